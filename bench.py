@@ -11,11 +11,22 @@ update (K3).  Inputs are resident in HBM before timing starts.  N > 1 shards
 the SAME window's landmarks across ranks (strong scaling, one all-reduce per
 iteration).  Rank 0 prints ONE JSON line.
 
-Also reported in that line: the per-kernel HIP-event durations measured on
-the library stream over the timed region, the roofline of the dominant
-kernel, the CPU baseline (the C oracle, timed on this host's cores) and, at
-N = 1, the secondary metric "descriptor-match Mpairs/sec" (SIFT-like 4000 x
-4000 x 128 frame pairs, batched, int8 MFMA path) with its own roofline.
+A plain run does only what the headline figure needs: set-up, W warm-up
+iterations, ONE timed region of K iterations, a status check, the line.
+``--dump-outputs DIR`` also writes the state the timed region left (what a
+caller of ``BASession.get_state`` receives after it) as ``DIR/poses.npy`` and
+``DIR/points.npy`` (float64); the window is seeded, so the same arguments give
+the same inputs on every run.
+
+``--full`` adds everything else to that line: three timed regions (the value
+is then the median region's rate), the per-kernel HIP-event durations measured
+on the library stream over a further region, the roofline of the dominant
+kernel, the parity guard against the C oracle, the CPU baseline (the C oracle,
+timed on this host's cores) and, at N = 1, the secondary metric
+"descriptor-match Mpairs/sec" (SIFT-like 4000 x 4000 x 128 frame pairs,
+batched, int8 MFMA path) with its own roofline, the float matcher,
+triangulation, PnP-RANSAC and SIFT lines.  ``--no-cpu-baseline`` and
+``--no-matcher`` trim a ``--full`` run.
 """
 
 from __future__ import annotations
@@ -525,6 +536,71 @@ def bench_sift(ctx, batch: int = 8, h: int = 376, w: int = 1241, calls: int = 10
     return res
 
 
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """``--dump-outputs``: every array as ``<out_dir>/<name>.npy``, float64 (float32 stays float32)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        np.save(out / f"{name}.npy", a if a.dtype == np.float32 else a.astype(np.float64))
+
+
+def full_report(line: dict, args, ctx, sess, p, pts, p0: int, p1: int, ptr, stats: dict, prof: dict,
+                dt_prof: float, world: int, rank: int) -> int:
+    """``--full``: adds the parity guard, the per-kernel figures and rooflines of the BA iteration,
+    the CPU baseline and the other workloads' lines to ``line``; non-zero when the guard fails."""
+    # parity guard (not timed): the same build from the window's start state, 2 iterations,
+    # against the C oracle at the north-star tolerance -- a wrong-result build prints no number
+    guard = ba_parity_guard(sess, p, pts, p0, p1, args.lam)
+    if not guard["ok"]:
+        print(f"error: BA parity guard failed: {guard}", file=sys.stderr)
+        return 1
+
+    n_free = p.n_poses - p.n_fixed
+    kern = {}
+    best = None
+    for k, (ms, cnt) in prof.items():
+        avg_us = ms / cnt * 1e3
+        kern[k] = {"avg_us": round(avg_us, 3), "launches": cnt, "total_ms": round(ms, 3)}
+        if best is None or ms > prof[best][0]:
+            best = k
+    nbytes = ba_kernel_bytes(best, p.n_poses, p1 - p0, int(ptr[-1]), n_free, stats["profile_blocks"])
+    if best == "ba_solve" and "ba_reduce" not in prof:  # K2 fused into K3's launch (one rank)
+        nbytes += ba_kernel_bytes("ba_reduce", p.n_poses, p1 - p0, int(ptr[-1]), n_free, stats["profile_blocks"])
+    avg_s = prof[best][0] / prof[best][1] / 1e3
+    achieved = nbytes / avg_s / 1e9
+    tpath = args.traffic_json or str(ROOT / "profiles" / f"traffic_{args.config}.json")
+    ba_traffic, traffic_why = traffic_for(tpath, args.config, args.lam, world, "ba", sorted(prof))
+    traffic = ba_traffic.get(best)
+    lin_bytes = ba_kernel_bytes("ba_lin", p.n_poses, p1 - p0, int(ptr[-1]), n_free, stats["profile_blocks"])
+    lin_avg = prof["ba_lin"][0] / prof["ba_lin"][1] / 1e3
+    line.update({
+        "ms_per_step_with_kernel_events": dt_prof / args.steps * 1e3,
+        "kernels": kern,
+        "roofline": {
+            "bound": "hbm", "kernel": best, "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_note": traffic_why, "traffic_file": tpath, "traffic_all_kernels": ba_traffic or None,
+            "bytes_per_launch": nbytes,
+            "note": "algorithmic bytes per launch / HIP-event average duration on the library stream",
+        },
+        "roofline_ba_lin": {"achieved": lin_bytes / lin_avg / 1e9, "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": lin_bytes / lin_avg / 1e9 / HBM_PEAK_GBS,
+                            "bytes_per_launch": lin_bytes},
+        "parity_guard": guard,
+    })
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline_ba(p, args.lam)
+        line["speedup_vs_cpu_baseline"] = line["value"] / line["cpu_baseline"]["value"]
+    if rank == 0 and world == 1 and not args.no_matcher:
+        line["secondary"] = bench_matcher(ctx, traffic_path=tpath)
+        line["matcher_float"] = bench_matcher_float(ctx, traffic_path=tpath)
+        line["triangulate"] = bench_triangulate(ctx)
+        line["pnp"] = bench_pnp(ctx)
+        line["sift"] = bench_sift(ctx)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -532,8 +608,17 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=100)  # ~7 ms at cfg3: the clocks settle before the timed region
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--lam", type=float, default=1.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-matcher", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also: three timed regions (value = the median's rate), per-kernel HIP-event durations "
+                         "and rooflines, the parity guard against the C oracle, the CPU baseline and the matcher, "
+                         "triangulation, PnP and SIFT lines (a plain run times --steps iterations once and "
+                         "prints the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed iterations left (BASession.get_state: poses (N,4,4) and this "
+                         "rank's landmarks (L,3), float64) as DIR/poses.npy and DIR/points.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-matcher", action="store_true",
+                    help="with --full: skip the matcher, triangulation, PnP and SIFT lines")
     ap.add_argument("--k1", type=int, default=0,
                     help="tuning: K1 variant through the testing switch vo_ba_testing_k1 (0 = the product "
                          "default, -1 four-wave K1, n = 1..3 one-wave K1 with n chunks per segment)")
@@ -608,47 +693,29 @@ def main() -> int:
 
     sess.run_async(args.warmup)
     sess.synchronize()
-    # timed regions 1-3 (the metric): K iterations each, no event markers between the kernels;
-    # the value is the median region's rate (a transient of the box cannot set it),
-    # every region is reported
-    regions = [timed(args.steps, False) for _ in range(3)]
+    # the timed region (the metric): K iterations, no event markers between the kernels.  --full
+    # times three such regions and reports the median's rate (a transient of the
+    # box cannot set it); every region is reported
+    regions = [timed(args.steps, False) for _ in range(3 if args.full else 1)]
     dt = sorted(regions)[len(regions) // 2]
-    # timed region 2: the same K iterations with HIP events around every kernel on the
-    # library stream -> per-kernel average durations for the roofline
-    dt_prof = timed(args.steps, True)
-    prof = _lib.profile_read(ctx)
-    _lib.profile_enable(ctx, False)
+    # what the timed iterations computed: the state a caller reads back after them
+    final_state = sess.get_state() if args.dump_outputs else None
+    if args.full:
+        # a further region: the same K iterations with HIP events around every kernel on the
+        # library stream -> per-kernel average durations for the roofline
+        dt_prof = timed(args.steps, True)
+        prof = _lib.profile_read(ctx)
+        _lib.profile_enable(ctx, False)
     # guard: the timed iterations must not have failed (status is checked by a sync run)
     rc, costs = sess.run(1)
     if rc != _lib.VO_OK or not np.all(np.isfinite(costs)):
         print(f"error: BA status {rc}, costs {costs}", file=sys.stderr)
         return 1
-    # parity guard (not timed): the same build from the window's start state, 2 iterations,
-    # against the C oracle at the north-star tolerance -- a wrong-result build prints no number
-    guard = ba_parity_guard(sess, p, pts, p0, p1, args.lam)
-    if not guard["ok"]:
-        print(f"error: BA parity guard failed: {guard}", file=sys.stderr)
-        return 1
+    if final_state is not None:
+        name = "points" if world == 1 else f"points_rank{rank}"
+        dump_outputs(args.dump_outputs, {name: final_state[1], **({"poses": final_state[0]} if rank == 0 else {})})
 
     value = args.steps / dt
-    n_free = p.n_poses - p.n_fixed
-    kern = {}
-    best = None
-    for k, (ms, cnt) in prof.items():
-        avg_us = ms / cnt * 1e3
-        kern[k] = {"avg_us": round(avg_us, 3), "launches": cnt, "total_ms": round(ms, 3)}
-        if best is None or ms > prof[best][0]:
-            best = k
-    nbytes = ba_kernel_bytes(best, p.n_poses, p1 - p0, int(ptr[-1]), n_free, stats["profile_blocks"])
-    if best == "ba_solve" and "ba_reduce" not in prof:  # K2 fused into K3's launch (one rank)
-        nbytes += ba_kernel_bytes("ba_reduce", p.n_poses, p1 - p0, int(ptr[-1]), n_free, stats["profile_blocks"])
-    avg_s = prof[best][0] / prof[best][1] / 1e3
-    achieved = nbytes / avg_s / 1e9
-    tpath = args.traffic_json or str(ROOT / "profiles" / f"traffic_{args.config}.json")
-    ba_traffic, traffic_why = traffic_for(tpath, args.config, args.lam, world, "ba", sorted(prof))
-    traffic = ba_traffic.get(best)
-    lin_bytes = ba_kernel_bytes("ba_lin", p.n_poses, p1 - p0, int(ptr[-1]), n_free, stats["profile_blocks"])
-    lin_avg = prof["ba_lin"][0] / prof["ba_lin"][1] / 1e3
     line = {
         "metric": METRIC,
         "value": value,
@@ -657,8 +724,7 @@ def main() -> int:
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": dt / args.steps * 1e3,
-        "ms_per_step_with_kernel_events": dt_prof / args.steps * 1e3,
-        "timed_regions": {"steps_each": args.steps, "reported": "median",
+        "timed_regions": {"steps_each": args.steps, "reported": "median" if args.full else "single",
                           "ms_per_step": [r / args.steps * 1e3 for r in regions],
                           "value": [args.steps / r for r in regions]},
         "higher_is_better": True,
@@ -677,29 +743,12 @@ def main() -> int:
             "plan": stats,
             "reserve_ms": reserve_ms,
         },
-        "kernels": kern,
-        "roofline": {
-            "bound": "hbm", "kernel": best, "achieved": achieved, "peak": HBM_PEAK_GBS,
-            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-            "traffic_note": traffic_why, "traffic_file": tpath, "traffic_all_kernels": ba_traffic or None,
-            "bytes_per_launch": nbytes,
-            "note": "algorithmic bytes per launch / HIP-event average duration on the library stream",
-        },
-        "roofline_ba_lin": {"achieved": lin_bytes / lin_avg / 1e9, "peak": HBM_PEAK_GBS,
-                            "unit": "GB/s", "frac": lin_bytes / lin_avg / 1e9 / HBM_PEAK_GBS,
-                            "bytes_per_launch": lin_bytes},
         "algorithmic_bytes_per_iter": stats["algorithmic_bytes_per_iter"],
-        "parity_guard": guard,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline_ba(p, args.lam)
-        line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
-    if rank == 0 and world == 1 and not args.no_matcher:
-        line["secondary"] = bench_matcher(ctx, traffic_path=tpath)
-        line["matcher_float"] = bench_matcher_float(ctx, traffic_path=tpath)
-        line["triangulate"] = bench_triangulate(ctx)
-        line["pnp"] = bench_pnp(ctx)
-        line["sift"] = bench_sift(ctx)
+    if args.full:
+        rc = full_report(line, args, ctx, sess, p, pts, p0, p1, ptr, stats, prof, dt_prof, world, rank)
+        if rc:
+            return rc
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:

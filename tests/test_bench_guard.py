@@ -41,6 +41,16 @@ def test_guard_accepts_oracle_and_rejects_drift():
     assert not failed["ok"]
 
 
+def test_dump_outputs_writes_float_npy(tmp_path):
+    a = np.arange(12, dtype=np.float64).reshape(3, 4)[:, ::2]  # not contiguous
+    bench.dump_outputs(tmp_path / "d" / "e", {"a": a, "b": a.astype(np.float32), "c": np.arange(3)})
+    got = {f.stem: np.load(f) for f in (tmp_path / "d" / "e").iterdir()}
+    assert sorted(got) == ["a", "b", "c"]
+    assert got["a"].dtype == np.float64 and np.array_equal(got["a"], a)
+    assert got["b"].dtype == np.float32 and np.array_equal(got["b"], a)
+    assert got["c"].dtype == np.float64 and np.array_equal(got["c"], [0, 1, 2])
+
+
 def test_guard_checks_this_ranks_shard():
     p = make_ba_problem(6, 200, 9)
     L = p.points.shape[0]

@@ -18,8 +18,8 @@ for rep in 1 2; do
   for n in prod "$@"; do
     LIB=$PWD/visualodometry_amd/lib/libvo_hip_$n.so
     [ $n = prod ] && LIB=$PWD/visualodometry_amd/lib/libvo_hip.so
-    VO_LIB_PATH=$LIB timeout -k 10 120 python bench.py --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
-    VO_LIB_PATH=$LIB timeout -k 10 200 python bench.py --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
+    VO_LIB_PATH=$LIB timeout -k 10 120 python bench.py --full --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
+    VO_LIB_PATH=$LIB timeout -k 10 200 python bench.py --full --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
       > $OUT/cfg4_${n}_$rep.json 2> $OUT/cfg4_${n}_$rep.err
   done
 done

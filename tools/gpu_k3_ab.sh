@@ -21,7 +21,7 @@ for rep in 1 2 3; do
   for n in $BASE prod; do
     LIB=$L/libvo_hip_$n.so
     [ $n = prod ] && LIB=$L/libvo_hip.so
-    VO_LIB_PATH=$LIB timeout -k 10 120 python bench.py --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
+    VO_LIB_PATH=$LIB timeout -k 10 120 python bench.py --full --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
   done
 done
 if [ -n "${CFG4:-}" ]; then
@@ -29,7 +29,7 @@ if [ -n "${CFG4:-}" ]; then
     for n in $BASE prod; do
       LIB=$L/libvo_hip_$n.so
       [ $n = prod ] && LIB=$L/libvo_hip.so
-      VO_LIB_PATH=$LIB timeout -k 10 200 python bench.py --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
+      VO_LIB_PATH=$LIB timeout -k 10 200 python bench.py --full --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
         > $OUT/cfg4_${n}_$rep.json 2> $OUT/cfg4_${n}_$rep.err
     done
   done

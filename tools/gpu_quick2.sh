@@ -21,7 +21,7 @@ for rep in 1 2 3; do
   for n in $BASE prod; do
     LIB=$L/libvo_hip_$n.so
     [ $n = prod ] && LIB=$L/libvo_hip.so
-    VO_LIB_PATH=$LIB timeout -k 10 120 python bench.py --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
+    VO_LIB_PATH=$LIB timeout -k 10 120 python bench.py --full --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
   done
 done
 for n in $BASE prod; do

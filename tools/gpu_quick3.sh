@@ -24,12 +24,12 @@ fi
 timeout -k 10 180 python tools/frame_latency.py > $OUT/frame_latency.json 2> $OUT/frame_latency.err
 for rep in 1 2 3; do
   for n in $BASE prod "$@"; do
-    VO_LIB_PATH=$(lib $n) timeout -k 10 120 python bench.py --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
+    VO_LIB_PATH=$(lib $n) timeout -k 10 120 python bench.py --full --no-matcher --no-cpu-baseline > $OUT/cfg3_${n}_$rep.json 2> $OUT/cfg3_${n}_$rep.err
   done
 done
 for rep in 1 2; do
   for n in prod "$@"; do
-    VO_LIB_PATH=$(lib $n) timeout -k 10 200 python bench.py --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
+    VO_LIB_PATH=$(lib $n) timeout -k 10 200 python bench.py --full --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
       > $OUT/cfg4_${n}_$rep.json 2> $OUT/cfg4_${n}_$rep.err
   done
 done

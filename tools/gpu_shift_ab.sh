@@ -9,7 +9,7 @@ done
 for rep in 1 2 3; do
   for n in prod shift1 shift2; do
     LIB=$L/libvo_hip_$n.so; [ $n = prod ] && LIB=$L/libvo_hip.so
-    VO_LIB_PATH=$LIB timeout -k 10 200 python bench.py --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
+    VO_LIB_PATH=$LIB timeout -k 10 200 python bench.py --full --config cfg4 --no-matcher --no-cpu-baseline --steps 50 --warmup 5 \
       > $OUT/cfg4_${n}_$rep.json 2> $OUT/cfg4_${n}_$rep.err
   done
 done

@@ -8,7 +8,7 @@ timeout -k 10 180 python tools/frame_latency.py > $OUT/frame_latency.json 2> $OU
 for rep in 1 2; do
   for n in c1 prod; do
     LIB=$L/libvo_hip_$n.so; [ $n = prod ] && LIB=$L/libvo_hip.so
-    VO_LIB_PATH=$LIB timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_${n}_$rep.json 2> $OUT/bench_${n}_$rep.err
+    VO_LIB_PATH=$LIB timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_${n}_$rep.json 2> $OUT/bench_${n}_$rep.err
   done
 done
 echo done
