@@ -116,6 +116,33 @@ int vo_match_knn2(vo_ctx* ctx, const float* des0, int n0, const float* des1, int
 int vo_match_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1,
                          int batch, int n0, int n1, int dim, double ratio,
                          int32_t* d_best);
+
+/* Mutual-check matching: the ratio test above plus OpenCV's BFMatcher(crossCheck=True) rule
+ * (the brute-force stand-in for a one-to-one learned matcher: the VO loop indexes
+ * keyframe["ids"][ref_indices], vo.py:66,121,252-288, which needs one-to-one pairs).
+ *   Forward pass: unchanged -- top-2 per query under keys (sqrtf(d2), j), equal distances
+ *   keep the lower j; (i, j1) kept iff (double)dist1 < ratio * (double)dist2; queries with
+ *   fewer than 2 neighbours emit nothing.
+ *   Cross check: a kept pair (i, j) survives iff i is the nearest query row of train row j
+ *   under keys (sqrtf(d2(i', j)), i') over all query rows i' -- equal distances keep the lower
+ *   query index.  The distances are the forward pass's arithmetic (the exact integer d2 on
+ *   the int8 path, the k-ordered fmaf chain on the float path); (a-b)^2 and (b-a)^2 are
+ *   bit-identical, so the reverse nearest is vo_match_knn2(des1, des0)'s first column.
+ * Output as vo_match_knn2_ratio's (ascending query order, capacity 2*n0 int32); no train index
+ * appears twice.  n0 == 0 or n1 == 0 gives *out_count = 0, n1 == 1 nothing (the forward rule),
+ * n0 == 1 is legal.  Results never depend on vo_match_hint, the query cache or the splits.
+ * flags: VO_MATCH_DEVICE_PTRS = des0 / des1 are device pointers, validated as
+ * vo_match_knn2_ratio_dev's (VO_ERR_ARG before any launch); otherwise host arrays.  A nonzero
+ * des0_tag keys the query cache as in _q: on a hit des0 is neither uploaded nor packed again,
+ * for either role it plays (query rows forward, columns in the reverse pass). */
+#define VO_MATCH_DEVICE_PTRS 1
+int vo_match_mutual(vo_ctx* ctx, const float* des0, int n0, uint64_t des0_tag, const float* des1,
+                    int n1, int dim, double ratio, int flags, int32_t* out_pairs, int32_t* out_count);
+/* vo_match_batch_async with the cross check: d_best (batch, n0) int32, the train index of each
+ * surviving pair or -1. */
+int vo_match_mutual_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1,
+                                int batch, int n0, int n1, int dim, double ratio,
+                                int32_t* d_best);
 /* Descriptor-kind hint for this context's later matcher calls (results never depend on
  * it; the device checks every call's values either way):
  *   VO_DESC_AUTO (0, default) launches both paths' kernels; a call runs the one its

@@ -26,6 +26,7 @@ VO_ERR_RCCL = -4
 VO_ERR_NOMEM = -5
 VO_ERR_STATE = -6
 VO_ERR_NODEV = -7
+VO_MATCH_DEVICE_PTRS = 1  # vo_match_mutual flags
 STATUS_NAMES = {
     VO_OK: "ok", VO_ERR_ARG: "bad argument", VO_ERR_HIP: "HIP error",
     VO_ERR_NOT_SPD: "not positive definite", VO_ERR_RCCL: "RCCL error",
@@ -76,6 +77,8 @@ SIGNATURES = {
     "vo_match_knn2_ratio_dev": (_I, [_P, C.c_void_p, _I, C.c_uint64, C.c_void_p, _I, _I, _D, _PI32, _PI32]),
     "vo_match_knn2": (_I, [_P, _PF, _I, _PF, _I, _I, _PI32, _PF]),
     "vo_match_batch_async": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P]),
+    "vo_match_mutual": (_I, [_P, C.c_void_p, _I, C.c_uint64, C.c_void_p, _I, _I, _D, _I, _PI32, _PI32]),
+    "vo_match_mutual_batch_async": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P]),
     "vo_match_hint": (_I, [_P, _I]),
     "vo_ba_setup": (_I, [_P, C.POINTER(BAProblemC), C.POINTER(C.c_uint64)]),
     "vo_ba_set_state": (_I, [_P, C.c_uint64, _PD, _PD]),

@@ -110,7 +110,7 @@ void check_device_range(vo_ctx* ctx, const void* p, size_t bytes, const char* wh
 
 void match_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
                 double ratio, int32_t* pairs, int32_t* count, int32_t* idx2, float* dist2, uint64_t q_tag = 0,
-                bool device_src = false) {
+                bool device_src = false, bool mutual = false) {
   VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "match: bad shape n0=%d n1=%d dim=%d",
              n0, n1, dim);
   VO_REQUIRE((n0 == 0 || des0) && (n1 == 0 || des1), VO_ERR_ARG, "match: null descriptors");
@@ -161,7 +161,15 @@ void match_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n
     d_idx2 = ws.top2.as<int32_t>();
     d_dist2 = reinterpret_cast<float*>(d_idx2 + 2 * (size_t)n0);
   }
-  match_run(ctx, d0, d1, 1, n0, n1, dim, ratio, ws.best.as<int32_t>(), d_idx2, d_dist2, use_cache ? &qc : nullptr);
+  // the cross check: the reverse pass's nearest query per train row, then the filter over best
+  int32_t* d_rev = nullptr;
+  if (mutual && n1 > 0) {
+    ws.rev.reserve((size_t)n1 * 4);
+    d_rev = ws.rev.as<int32_t>();
+  }
+  match_run(ctx, d0, d1, 1, n0, n1, dim, ratio, ws.best.as<int32_t>(), d_idx2, d_dist2, use_cache ? &qc : nullptr,
+            d_rev);
+  if (d_rev) mutual_filter(ctx, ws.best.as<int32_t>(), d_rev, 1, n0, n1);
   if (pairs) {
     ws.pairs.reserve((size_t)n0 * 8 + 16);
     int32_t* d_pairs = ws.pairs.as<int32_t>();
@@ -618,6 +626,39 @@ int vo_match_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1, 
     VO_REQUIRE(d_best && (n0 == 0 || d_des0) && (n1 == 0 || d_des1), VO_ERR_ARG,
                "vo_match_batch_async: null pointers");
     vo::match_run(ctx, d_des0, d_des1, batch, n0, n1, dim, ratio, d_best, nullptr, nullptr);
+  });
+}
+
+int vo_match_mutual(vo_ctx* ctx, const float* des0, int n0, uint64_t des0_tag, const float* des1, int n1, int dim,
+                    double ratio, int flags, int32_t* out_pairs, int32_t* out_count) {
+  return guarded([&] {
+    vo::bind(ctx);
+    VO_REQUIRE(out_pairs && out_count, VO_ERR_ARG, "vo_match_mutual: null outputs");
+    VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "vo_match_mutual: bad shape");
+    VO_REQUIRE((flags & ~VO_MATCH_DEVICE_PTRS) == 0, VO_ERR_ARG, "vo_match_mutual: unknown flags 0x%x", flags);
+    const bool dev = (flags & VO_MATCH_DEVICE_PTRS) != 0;
+    if (dev) {  // as vo_match_knn2_ratio_dev: refused before any launch
+      vo::check_device_range(ctx, des0, (size_t)n0 * dim * 4, "des0");
+      vo::check_device_range(ctx, des1, (size_t)n1 * dim * 4, "des1");
+    }
+    vo::match_host(ctx, des0, n0, des1, n1, dim, ratio, out_pairs, out_count, nullptr, nullptr, des0_tag, dev, true);
+  });
+}
+
+int vo_match_mutual_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0, int n1,
+                                int dim, double ratio, int32_t* d_best) {
+  return guarded([&] {
+    vo::bind(ctx);
+    VO_REQUIRE(d_best && (n0 == 0 || d_des0) && (n1 == 0 || d_des1), VO_ERR_ARG,
+               "vo_match_mutual_batch_async: null pointers");
+    VO_REQUIRE(batch >= 1 && n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "vo_match_mutual_batch_async: bad shape");
+    int32_t* d_rev = nullptr;
+    if (n0 > 0 && n1 > 0) {
+      ctx->match.rev.reserve((size_t)batch * n1 * 4);
+      d_rev = ctx->match.rev.as<int32_t>();
+    }
+    vo::match_run(ctx, d_des0, d_des1, batch, n0, n1, dim, ratio, d_best, nullptr, nullptr, nullptr, d_rev);
+    if (d_rev) vo::mutual_filter(ctx, d_best, d_rev, batch, n0, n1);
   });
 }
 

@@ -20,6 +20,11 @@
 //
 // Float path (any other values, e.g. SuperPoint): d2 is the k-ordered fmaf
 // chain sum((a_k - b_k)^2) in fp32 and keys are (sqrtf(d2), j) directly.
+//
+// Cross check (vo_match_mutual*): after the forward pass the same sweeps run with the roles
+// swapped and top-1 only -- (a-b)^2 == (b-a)^2 bit for bit, so the reverse nearest of train
+// row j is the forward rule applied to (des1, des0) -- and mutual_filter_kernel drops every
+// kept pair (i, j) whose train row's nearest query is not i.
 #include "match_short.h"
 #include <type_traits>
 
@@ -81,6 +86,12 @@ __device__ __forceinline__ uint32_t max3_u32(uint32_t a, uint32_t b, uint32_t c)
   return r;
 }
 
+// The same reduction for one key per lane (the cross check's reverse pass keeps the nearest only)
+template <int Ctrl>
+__device__ __forceinline__ void row_top1_step(uint32_t& M1) {
+  M1 = max(M1, (uint32_t)__builtin_amdgcn_mov_dpp((int)M1, Ctrl, 0xF, 0xF, false));
+}
+
 // One step of a 16-lane top-2 reduction on u32 keys (larger = better): merge this
 // lane's (M1 >= M2) with the pair of the lane `Ctrl` (a DPP row rotation) away.
 // second(a1, a2, b1, b2) = med3(a1, b1, max(a2, b2)) since max(a2, b2) <= max(a1, b1).
@@ -126,7 +137,7 @@ struct PackSide {
   long in_bstride, q_bstride;
   int8_t* q8;
   int* norms;
-  uint32_t* colconst;  // train side only
+  uint32_t* colconst;  // the side a sweep takes as its columns (both under the cross check)
 };
 
 __global__ __launch_bounds__(256) void pack_kernel(PackSide sa, PackSide sb, int dim, int Dp,
@@ -183,7 +194,7 @@ __global__ __launch_bounds__(256) void pack_kernel(PackSide sa, PackSide sb, int
   if (__any(nonfinite) && (threadIdx.x & 63) == 0) flag[1] = gen;  // the exact sweep handles it
   if (sub == 0) {
     P.norms[b * (long)P.n_pad + row] = acc;
-    if (is_b) {
+    if (P.colconst) {
       P.colconst[b * (long)P.n_pad + row] =
           live_row ? ((max_off(Dp) - (uint32_t)acc) << 8) | (255u - ((uint32_t)(row >> 4) & 255u)) : 0u;
     }
@@ -205,7 +216,9 @@ struct MatchArgs {
   int n0, n1, dim, Dp, n0_pad, n1_pad, split_w, force_f32;
   int short_ok;  // float calls take the bf16 shortlist (match_bf16.hip) unless non-finite
   int exact_in_merge;  // int8 launch: merge_kernel runs the exact fp32 sweep for float values
+  int top1;  // reverse pass of the cross check: only the nearest column is kept
   long qa_bstride, qb_bstride, a_bstride, b_bstride;
+  long cc_bstride, na_bstride;  // colconst / norma entries per frame pair
   uint4* partial;
   const uint32_t* flag;
   uint32_t gen;
@@ -213,6 +226,7 @@ struct MatchArgs {
   int32_t* best;
   int32_t* idx2;
   float* dist2;
+  int32_t* rev;  // top1: (batch, n0) nearest column, -1 = none
 };
 
 // Slot swizzle of the B chunk image (see sweep_i8), found by exhaustive search over strides
@@ -226,7 +240,9 @@ __device__ __forceinline__ int i8_swz(int row) {
 }
 
 // int8 MFMA sweep of one workgroup: 4 waves x 64 query rows
-template <int KS>
+// TOP1 (the cross check's reverse pass, roles swapped): the running top-2's med3 + max per
+// key become one max (two keys: one max3), and the lane merge keeps one key.
+template <int KS, bool TOP1>
 __device__ __forceinline__ void sweep_i8(const MatchArgs& p) {
   const int8_t* qa = p.qa;
   const int8_t* qb = p.qb;
@@ -245,7 +261,7 @@ __device__ __forceinline__ void sweep_i8(const MatchArgs& p) {
   const int rowbase = blockIdx.x * kRowsPerWG + wave * kRowsPerWave;
   const int8_t* A = qa + b * qa_bstride;
   const int8_t* B = qb + b * qb_bstride;
-  const uint32_t* cc = colconst + b * (long)n1_pad;
+  const uint32_t* cc = colconst + b * p.cc_bstride;
 
   v4i afrag[kMT][KS];
 #pragma unroll
@@ -347,7 +363,7 @@ __device__ __forceinline__ void sweep_i8(const MatchArgs& p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const uint32_t p = ((uint32_t)a.v[mt][r] << 9) + ccol;
-        m2[mt][r] = med3_u32(m1[mt][r], m2[mt][r], p);
+        if constexpr (!TOP1) m2[mt][r] = med3_u32(m1[mt][r], m2[mt][r], p);
         m1[mt][r] = max(m1[mt][r], p);
       }
   };
@@ -361,7 +377,7 @@ __device__ __forceinline__ void sweep_i8(const MatchArgs& p) {
       for (int r = 0; r < 4; ++r) {
         const uint32_t p = ((uint32_t)a.v[mt][r] << 9) + ca;
         const uint32_t q = ((uint32_t)b.v[mt][r] << 9) + cbk;
-        m2[mt][r] = max(m2[mt][r], med3_u32(m1[mt][r], p, q));
+        if constexpr (!TOP1) m2[mt][r] = max(m2[mt][r], med3_u32(m1[mt][r], p, q));
         m1[mt][r] = max3_u32(m1[mt][r], p, q);
       }
   };
@@ -411,10 +427,18 @@ __device__ __forceinline__ void sweep_i8(const MatchArgs& p) {
     for (int r = 0; r < 4; ++r) {
       const uint32_t a1 = m1[mt][r], a2 = m2[mt][r];
       uint32_t M1 = a1, M2 = a2;
-      row_top2_step<0x121>(M1, M2);  // row_ror:1
-      row_top2_step<0x122>(M1, M2);  // row_ror:2
-      row_top2_step<0x124>(M1, M2);  // row_ror:4
-      row_top2_step<0x128>(M1, M2);  // row_ror:8
+      if constexpr (TOP1) {
+        row_top1_step<0x121>(M1);
+        row_top1_step<0x122>(M1);
+        row_top1_step<0x124>(M1);
+        row_top1_step<0x128>(M1);
+        M2 = 0u;  // no second key: the partial's second slot stays empty
+      } else {
+        row_top2_step<0x121>(M1, M2);  // row_ror:1
+        row_top2_step<0x122>(M1, M2);  // row_ror:2
+        row_top2_step<0x124>(M1, M2);  // row_ror:4
+        row_top2_step<0x128>(M1, M2);  // row_ror:8
+      }
       const uint32_t g1 = (uint32_t)(__ballot(a1 == M1) >> gshift) & 0xFFFFu;
       const uint32_t g2 = (uint32_t)(__ballot(a1 == M2 || a2 == M2) >> gshift) & 0xFFFFu;
       const uint32_t l1 = __builtin_ctz(g1 | 0x10000u);
@@ -422,7 +446,7 @@ __device__ __forceinline__ void sweep_i8(const MatchArgs& p) {
       const uint32_t l2 = __builtin_ctz((M2 == M1 ? g1 & ~(1u << l1) : g2) | 0x10000u);
       if ((lane & 15) == 0) {
         const int row = rowbase + mt * 16 + (lane >> 4) * 4 + r;
-        const int na = norma[b * (long)n0_pad + row];
+        const int na = norma[b * p.na_bstride + row];
         uint4 q = make_uint4(~0u, ~0u, ~0u, ~0u);
         if (M1 != 0u) {
           q.x = kOffMax - (M1 >> 8) + na;
@@ -565,7 +589,9 @@ __global__ __launch_bounds__(256) void merge_kernel(MatchArgs p, int nsplit) {
   if (!fpath) {
     // (d2, j) order equals (sqrtf(d2), j) order unless sqrtf merges two
     // consecutive integers, which needs d2 >= 2^22 (see header).
-    const bool rescan = row < p.n0 && k2 != ~0ull && (uint32_t)(k2 >> 32) >= (uint32_t)kCollide;
+    // top1 partials hold one key: the nearest can change only if its own d2 reaches 2^22
+    const uint64_t kr = p.top1 ? k1 : k2;
+    const bool rescan = row < p.n0 && kr != ~0ull && (uint32_t)(kr >> 32) >= (uint32_t)kCollide;
     uint64_t todo = __ballot(rescan);
     if (rescan) {
       k1 = k2 = ~0ull;
@@ -606,6 +632,7 @@ __global__ __launch_bounds__(256) void merge_kernel(MatchArgs p, int nsplit) {
     const int j2 = k2 == ~0ull ? -1 : (int)(uint32_t)k2;
     const long o = (long)b * p.n0 + row;
     if (p.best) p.best[o] = (j2 >= 0 && (double)s1 < p.ratio * (double)s2) ? j1 : -1;
+    if (p.rev) p.rev[o] = j1;
     if (p.idx2) {
       p.idx2[2 * o] = j1;
       p.idx2[2 * o + 1] = j2;
@@ -618,10 +645,10 @@ __global__ __launch_bounds__(256) void merge_kernel(MatchArgs p, int nsplit) {
 // The int8 sweep only: a call whose values are not SIFT integers (decided on the device by
 // pack_kernel) takes the exact fp32 sweep inside merge_kernel, so this kernel's registers and
 // LDS are its own, not the maximum of both paths'.
-template <int KS>
+template <int KS, bool TOP1>
 __global__ __launch_bounds__(kMatchThreads) void match_kernel(MatchArgs p) {
   const bool fpath = p.force_f32 || p.flag[0] == p.gen;  // uniform
-  if (!fpath) sweep_i8<KS>(p);
+  if (!fpath) sweep_i8<KS, TOP1>(p);
 }
 
 // descriptors wider than the int8 kernel takes (Dp > 256): the exact fp32 sweep is the path
@@ -676,26 +703,66 @@ __global__ __launch_bounds__(1024) void compact_kernel(const int32_t* __restrict
   if (threadIdx.x == 0) *count = base;
 }
 
+// ---- cross check ---------------------------------------------------------------
+// rev[j] = the nearest query row of train row j under keys (sqrtf(d2(i', j)), i') (the reverse
+// pass: the same sweeps with the roles swapped).  A ratio-kept pair (i, best[i]) survives iff
+// rev[best[i]] == i; runs before compact_kernel.
+__global__ __launch_bounds__(256) void mutual_filter_kernel(int32_t* __restrict__ best,
+                                                            const int32_t* __restrict__ rev, int n0, int n1,
+                                                            int total) {
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  if (o >= total) return;
+  const int b = o / n0, i = o - b * n0;
+  const int j = best[o];
+  if (j < 0) return;
+  best[o] = (j < n1 && rev[(long)b * n1 + j] == i) ? j : -1;
+}
+
 int pow2_floor(int x) {
   int p = 1;
   while (p * 2 <= x) p *= 2;
   return p;
 }
 
+// One pass's shape: n0 rows (the M side, padded to 256) against n1 columns (the N side, padded
+// to 16), and the column split that fills the chip (w | 4096, w >= 256); the split count does
+// not change any result (splits merge on exact (d^2, j) keys)
+struct PassShape {
+  int n0, n1, n0_pad, n1_pad, row_wgs, w, nsplit;
+};
+
+PassShape pass_shape(const vo_ctx* ctx, int batch, int n0, int n1) {
+  PassShape s;
+  s.n0 = n0;
+  s.n1 = n1;
+  s.n0_pad = ceil_div(std::max(n0, 1), kRowsPerWG) * kRowsPerWG;
+  s.n1_pad = ceil_div(std::max(n1, 1), 16) * 16;
+  s.row_wgs = s.n0_pad / kRowsPerWG;
+  constexpr int wgs_per_cu = VO_MATCH_WGS_PER_CU;  // tuning builds: EXTRA=-DVO_MATCH_WGS_PER_CU=n
+  const int want = std::max(1, ceil_div(wgs_per_cu * ctx->num_cus, (int64_t)s.row_wgs * batch));
+  int w = pow2_floor(std::max(1, s.n1_pad / want));
+  s.w = std::max(256, std::min(4096, w));
+  s.nsplit = std::max(1, ceil_div(s.n1_pad, s.w));
+  return s;
+}
+
 }  // namespace
 
 // Packs one query side (batch 1) into the cache's own buffers, with its own flag words
 // (generation 1: [0] = 1 if a value is not an integer in [0, 255], [1] = 1 if one is not finite).
+// Its column constants are kept too: under the cross check the cached side is the reverse
+// pass's columns.
 void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc) {
   hipStream_t st = ctx->stream;
   const int Dp = ceil_div(dim, kKStep) * kKStep;
   const int n0_pad = ceil_div(std::max(n0, 1), kRowsPerWG) * kRowsPerWG;
   qc.q8.reserve((size_t)n0_pad * Dp);
   qc.norms.reserve((size_t)n0_pad * sizeof(int));
+  qc.colconst.reserve((size_t)n0_pad * sizeof(uint32_t));
   qc.flag.reserve(2 * sizeof(uint32_t));
   VO_HIP_CHECK(hipMemsetAsync(qc.flag.ptr, 0, 2 * sizeof(uint32_t), st));
   PackSide pa{d_des0, n0, n0_pad, ceil_div((int64_t)n0_pad * 16, 256), (long)n0 * dim, (long)n0_pad * Dp,
-              qc.q8.as<int8_t>(), qc.norms.as<int>(), nullptr};
+              qc.q8.as<int8_t>(), qc.norms.as<int>(), qc.colconst.as<uint32_t>()};
   PackSide pb{nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, nullptr};
   const int vec4 = dim % 4 == 0 && (uintptr_t)d_des0 % 16 == 0;
   ctx->prof.begin(st, kKMatchPack);
@@ -705,9 +772,14 @@ void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQu
   VO_HIP_CHECK(hipGetLastError());
 }
 
+// d_rev != nullptr (the cross check, n1 > 0): after the forward pass the same sweeps run with
+// the roles swapped (train rows the M side, query rows the columns; top-1 only) and write
+// d_rev (batch, n1), the nearest query row of every train row.  Both passes read one pack of
+// each side: the int8 images, norms and column constants are packed once, each side padded
+// to the 256 rows it needs as an M side.
 void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0,
                int n1, int dim, double ratio, int32_t* d_best, int32_t* d_idx2,
-               float* d_dist2, const MatchQueryCache* qc) {
+               float* d_dist2, const MatchQueryCache* qc, int32_t* d_rev) {
   VO_REQUIRE(batch >= 1 && n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG,
              "match: bad shape batch=%d n0=%d n1=%d dim=%d", batch, n0, n1, dim);
   if (n0 == 0) return;
@@ -715,20 +787,15 @@ void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch,
   MatchWorkspace& ws = ctx->match;
   const int Dp = ceil_div(dim, kKStep) * kKStep;
   const bool int_ok = Dp <= kMaxDpInt;
-  const int n0_pad = ceil_div(n0, kRowsPerWG) * kRowsPerWG;
-  const int n1_pad = ceil_div(std::max(n1, 1), 16) * 16;
-
-  // split the train columns so the grid fills the chip (w | 4096, w >= 64); the split
-  // count does not change any result (splits merge on exact (d^2, j) keys)
-  const int row_wgs = n0_pad / kRowsPerWG;
-  constexpr int wgs_per_cu = VO_MATCH_WGS_PER_CU;  // tuning builds: EXTRA=-DVO_MATCH_WGS_PER_CU=n
-  const int want = std::max(1, ceil_div(wgs_per_cu * ctx->num_cus, (int64_t)row_wgs * batch));
-  int w = pow2_floor(std::max(1, n1_pad / want));
-  w = std::max(256, std::min(4096, w));
-  const int nsplit = std::max(1, ceil_div(n1_pad, w));
+  const bool mutual = d_rev != nullptr && n1 > 0;
+  const PassShape F = pass_shape(ctx, batch, n0, n1);
+  const PassShape R = mutual ? pass_shape(ctx, batch, n1, n0) : F;
+  // rows the train side's images hold: its padding as the reverse pass's M side, if there is one
+  const int n1_rows = mutual ? R.n0_pad : F.n1_pad;
 
   ws.flag.reserve(2 * sizeof(uint32_t));
-  ws.partial.reserve((size_t)batch * nsplit * n0_pad * sizeof(uint4));
+  ws.partial.reserve((size_t)batch * std::max((size_t)F.nsplit * F.n0_pad, (size_t)R.nsplit * R.n0_pad) *
+                     sizeof(uint4));
   // generation tag of this call (see pack_kernel); 0 is the reset value of the flag
   if (++ws.gen == 0 || ws.flag_fresh) {
     VO_HIP_CHECK(hipMemsetAsync(ws.flag.ptr, 0, 2 * sizeof(uint32_t), st));
@@ -737,34 +804,39 @@ void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch,
   }
   uint32_t* flag = ws.flag.as<uint32_t>();
 
-  MatchArgs a{};
-  a.da = d_des0;
-  a.db = d_des1;
-  a.n0 = n0;
-  a.n1 = n1;
-  a.dim = dim;
-  a.Dp = Dp;
-  a.n0_pad = n0_pad;
-  a.n1_pad = n1_pad;
-  a.split_w = w;
   // dim <= 256: the shortlist's A fragments fit in VGPRs; a SIFT hint leaves it unlaunched
   // (float values then take the exact sweep).  A float hint skips the int8 pack and its
   // integer check: the shortlist is exact for any finite values, SIFT integers included (their
   // fp32 chains of <= 256 squared byte differences stay below 2^24, so F = the integer d^2 and
   // the (sqrtf, j) keys order as the integer path's), and fpack flags non-finite values itself.
   const bool float_hint = int_ok && ws.kind_hint == VO_DESC_FLOAT;
-  a.force_f32 = int_ok && !float_hint ? 0 : 1;
-  a.short_ok = int_ok && ws.kind_hint != VO_DESC_SIFT ? 1 : 0;
-  a.exact_in_merge = int_ok ? 1 : 0;
-  a.a_bstride = (long)n0 * dim;
-  a.b_bstride = (long)n1 * dim;
-  a.partial = ws.partial.as<uint4>();
-  a.flag = flag;
-  a.gen = ws.gen;
-  a.ratio = ratio;
-  a.best = d_best;
-  a.idx2 = d_idx2;
-  a.dist2 = d_dist2;
+  const bool short_ok = int_ok && ws.kind_hint != VO_DESC_SIFT;
+  auto base_args = [&](const PassShape& S, const float* da, const float* db) {
+    MatchArgs a{};
+    a.da = da;
+    a.db = db;
+    a.n0 = S.n0;
+    a.n1 = S.n1;
+    a.dim = dim;
+    a.Dp = Dp;
+    a.n0_pad = S.n0_pad;
+    a.n1_pad = S.n1_pad;
+    a.split_w = S.w;
+    a.force_f32 = int_ok && !float_hint ? 0 : 1;
+    a.short_ok = short_ok ? 1 : 0;
+    a.exact_in_merge = int_ok ? 1 : 0;
+    a.a_bstride = (long)S.n0 * dim;
+    a.b_bstride = (long)S.n1 * dim;
+    a.partial = ws.partial.as<uint4>();
+    a.flag = flag;
+    a.gen = ws.gen;
+    a.ratio = ratio;
+    return a;
+  };
+  MatchArgs fa = base_args(F, d_des0, d_des1);
+  fa.best = d_best;
+  fa.idx2 = d_idx2;
+  fa.dist2 = d_dist2;
   if (n1 == 0) {
     const int total = batch * n0;
     hipLaunchKernelGGL(no_train_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, total,
@@ -772,97 +844,139 @@ void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch,
     VO_HIP_CHECK(hipGetLastError());
     return;
   }
+  MatchArgs ra = base_args(R, d_des1, d_des0);
+  ra.top1 = 1;
+  ra.rev = d_rev;
   if (int_ok && !float_hint) {
     // a cached query side (batch 1: match_pack_query packed it for an earlier call) is read
     // from the cache's buffers; only the train side is packed
     const bool cached = qc != nullptr && batch == 1;
-    a.qa_bstride = (long)n0_pad * Dp;
-    a.qb_bstride = (long)n1_pad * Dp;
-    ws.q8.reserve((size_t)batch * (a.qa_bstride + a.qb_bstride));
-    ws.norms.reserve((size_t)batch * (n0_pad + n1_pad) * sizeof(int));
-    ws.colconst.reserve((size_t)batch * n1_pad * sizeof(uint32_t));
+    fa.qa_bstride = (long)F.n0_pad * Dp;
+    fa.qb_bstride = (long)n1_rows * Dp;
+    ws.q8.reserve((size_t)batch * (fa.qa_bstride + fa.qb_bstride));
+    ws.norms.reserve((size_t)batch * (F.n0_pad + n1_rows) * sizeof(int));
+    ws.colconst.reserve((size_t)batch * (n1_rows + (mutual ? F.n0_pad : 0)) * sizeof(uint32_t));
     int8_t* qa = cached ? qc->q8.as<int8_t>() : ws.q8.as<int8_t>();
-    int8_t* qb = ws.q8.as<int8_t>() + batch * a.qa_bstride;
+    int8_t* qb = ws.q8.as<int8_t>() + batch * fa.qa_bstride;
     int* na = cached ? qc->norms.as<int>() : ws.norms.as<int>();
-    int* nb = ws.norms.as<int>() + (size_t)batch * n0_pad;
-    a.qa = qa;
-    a.qb = qb;
-    a.colconst = ws.colconst.as<uint32_t>();
-    a.norma = na;
-    PackSide pa{d_des0, n0, n0_pad, cached ? 0 : ceil_div((int64_t)n0_pad * 16, 256), a.a_bstride,
-                a.qa_bstride, qa, na, nullptr};
-    PackSide pb{d_des1, n1, n1_pad, ceil_div((int64_t)n1_pad * 16, 256), a.b_bstride,
-                a.qb_bstride, qb, nb, ws.colconst.as<uint32_t>()};
+    int* nb = ws.norms.as<int>() + (size_t)batch * F.n0_pad;
+    uint32_t* ccb = ws.colconst.as<uint32_t>();
+    uint32_t* cca = !mutual ? nullptr : cached ? qc->colconst.as<uint32_t>() : ccb + (size_t)batch * n1_rows;
+    fa.qa = qa;
+    fa.qb = qb;
+    fa.colconst = ccb;
+    fa.norma = na;
+    fa.cc_bstride = n1_rows;
+    fa.na_bstride = F.n0_pad;
+    ra.qa = qb;
+    ra.qb = qa;
+    ra.colconst = cca;
+    ra.norma = nb;
+    ra.qa_bstride = fa.qb_bstride;
+    ra.qb_bstride = fa.qa_bstride;
+    ra.cc_bstride = F.n0_pad;
+    ra.na_bstride = n1_rows;
+    PackSide pa{d_des0, n0, F.n0_pad, cached ? 0 : ceil_div((int64_t)F.n0_pad * 16, 256), fa.a_bstride,
+                fa.qa_bstride, qa, na, cca};
+    PackSide pb{d_des1, n1, n1_rows, ceil_div((int64_t)n1_rows * 16, 256), fa.b_bstride,
+                fa.qb_bstride, qb, nb, ccb};
     const int vec4 = dim % 4 == 0 && (uintptr_t)d_des0 % 16 == 0 && (uintptr_t)d_des1 % 16 == 0;
     ctx->prof.begin(st, kKMatchPack);
     hipLaunchKernelGGL(pack_kernel, dim3(pa.wgs + pb.wgs, batch), dim3(256), 0, st, pa, pb, dim,
                        Dp, vec4, flag, ws.gen, cached ? qc->flag.as<uint32_t>() : (const uint32_t*)nullptr);
     ctx->prof.end(st);
   }
-  auto sweep = [&]() {  // int8 sweep, and the exact fp32 sweep (float calls the shortlist cannot take)
-    dim3 grid(row_wgs, nsplit, batch);
-    if (int_ok) {
-      ctx->prof.begin(st, kKMatchI8);
-      switch (Dp / kKStep) {
-        case 1: hipLaunchKernelGGL(match_kernel<1>, grid, dim3(kMatchThreads), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(match_kernel<2>, grid, dim3(kMatchThreads), 0, st, a); break;
-        case 3: hipLaunchKernelGGL(match_kernel<3>, grid, dim3(kMatchThreads), 0, st, a); break;
-        default: hipLaunchKernelGGL(match_kernel<4>, grid, dim3(kMatchThreads), 0, st, a); break;
-      }
-      ctx->prof.end(st);
-    } else {
-      ctx->prof.begin(st, kKMatchF32);
-      hipLaunchKernelGGL(match_f32_kernel, grid, dim3(256), 0, st, a);
-      ctx->prof.end(st);
+  if (short_ok) {
+    // the float path's buffers, sized for both passes before the first launch (no buffer
+    // grows between the passes)
+    const size_t sDp = short_Dp(dim);
+    for (const PassShape* S : {&F, &R}) {
+      ws.hbf.reserve((size_t)batch * (S->n0_pad + S->n1_pad) * sDp * 2);
+      ws.fnorm.reserve((size_t)batch * (S->n0_pad + S->n1_pad) * sizeof(float));
+      // (batch, nsplit_f, n0_pad) float2; short_launch picks nsplit_f <= ceil(n1_pad / 64)
+      ws.fpart.reserve((size_t)batch * ceil_div(S->n1_pad, 64) * S->n0_pad * sizeof(float2));
+      ws.cand.reserve((size_t)batch * (S->n0_pad / 32) * ceil_div(S->n1_pad, 64) * 64 * sizeof(uint32_t));
     }
-  };
-  // under the float hint no exact sweep or merge is launched: fpack raises the non-finite
-  // flag and frerank_kernel then answers the call by an exact scan itself
-  if (!float_hint) sweep();
-  if (a.short_ok) {  // float calls: bf16 MFMA shortlist + exact re-rank (match_bf16.hip)
-    ShortArgs s{};
-    s.da = d_des0;
-    s.db = d_des1;
-    s.n0 = n0;
-    s.n1 = n1;
-    s.dim = dim;
-    s.Dp = short_Dp(dim);
-    s.n0_pad = n0_pad;
-    s.n1_pad = n1_pad;
-    s.split_w = w;
-    s.nsplit = nsplit;
-    s.a_bstride = a.a_bstride;
-    s.b_bstride = a.b_bstride;
-    s.flag = flag;
-    s.gen = ws.gen;
-    s.forced = float_hint ? 1 : 0;
-    s.ratio = ratio;
-    s.best = d_best;
-    s.idx2 = d_idx2;
-    s.dist2 = d_dist2;
-    ws.hbf.reserve((size_t)batch * (n0_pad + n1_pad) * s.Dp * 2);
-    s.ha = ws.hbf.as<__bf16>();
-    s.hb = s.ha + (size_t)batch * n0_pad * s.Dp;
-    ws.fnorm.reserve((size_t)batch * (n0_pad + n1_pad) * sizeof(float));
-    s.nbq = ws.fnorm.as<float>();
-    s.ra = s.nbq + (size_t)batch * n1_pad;
     if (ws.bmax.bytes < (size_t)batch * kBmaxStride * sizeof(uint32_t)) {
       ws.bmax.reserve((size_t)batch * kBmaxStride * sizeof(uint32_t));
       VO_HIP_CHECK(hipMemsetAsync(ws.bmax.ptr, 0, ws.bmax.bytes, st));
     }
-    s.bmax = ws.bmax.as<uint32_t>();
-    // (batch, nsplit_f, n0_pad) float2; short_launch picks nsplit_f <= ceil(n1_pad / 64)
-    ws.fpart.reserve((size_t)batch * ceil_div(n1_pad, 64) * n0_pad * sizeof(float2));
-    s.part = ws.fpart.as<float2>();
-    ws.cand.reserve((size_t)batch * (n0_pad / 32) * ceil_div(n1_pad, 64) * 64 * sizeof(uint32_t));
-    s.mask = ws.cand.as<uint32_t>();
-    short_launch(ctx, s, batch);
   }
-  if (!float_hint) {
-    ctx->prof.begin(st, kKMatchMerge);
-    hipLaunchKernelGGL(merge_kernel, dim3(row_wgs, batch), dim3(256), 0, st, a, nsplit);
-    ctx->prof.end(st);
-  }
+  auto run_pass = [&](const MatchArgs& a, const PassShape& S) {
+    // int8 sweep, or the exact fp32 sweep (float calls the shortlist cannot take).  Under the
+    // float hint no exact sweep or merge is launched: fpack raises the non-finite flag and
+    // frerank_kernel then answers the call by an exact scan itself
+    if (!float_hint) {
+      dim3 grid(S.row_wgs, S.nsplit, batch);
+      if (int_ok) {
+        ctx->prof.begin(st, kKMatchI8);
+#define VO_I8_SWEEP(KS)                                                                          \
+  if (a.top1) hipLaunchKernelGGL((match_kernel<KS, true>), grid, dim3(kMatchThreads), 0, st, a); \
+  else hipLaunchKernelGGL((match_kernel<KS, false>), grid, dim3(kMatchThreads), 0, st, a);       \
+  break;
+        switch (Dp / kKStep) {
+          case 1: VO_I8_SWEEP(1)
+          case 2: VO_I8_SWEEP(2)
+          case 3: VO_I8_SWEEP(3)
+          default: VO_I8_SWEEP(4)
+        }
+#undef VO_I8_SWEEP
+        ctx->prof.end(st);
+      } else {
+        ctx->prof.begin(st, kKMatchF32);
+        hipLaunchKernelGGL(match_f32_kernel, grid, dim3(256), 0, st, a);
+        ctx->prof.end(st);
+      }
+    }
+    if (a.short_ok) {  // float calls: bf16 MFMA shortlist + exact re-rank (match_bf16.hip)
+      ShortArgs s{};
+      s.da = a.da;
+      s.db = a.db;
+      s.n0 = S.n0;
+      s.n1 = S.n1;
+      s.dim = dim;
+      s.Dp = short_Dp(dim);
+      s.n0_pad = S.n0_pad;
+      s.n1_pad = S.n1_pad;
+      s.split_w = S.w;
+      s.nsplit = S.nsplit;
+      s.a_bstride = a.a_bstride;
+      s.b_bstride = a.b_bstride;
+      s.flag = flag;
+      s.gen = ws.gen;
+      s.forced = float_hint ? 1 : 0;
+      s.ratio = ratio;
+      s.best = a.best;
+      s.idx2 = a.idx2;
+      s.dist2 = a.dist2;
+      s.rev = a.rev;
+      s.top1 = a.top1;
+      s.ha = ws.hbf.as<__bf16>();
+      s.hb = s.ha + (size_t)batch * S.n0_pad * s.Dp;
+      s.nbq = ws.fnorm.as<float>();
+      s.ra = s.nbq + (size_t)batch * S.n1_pad;
+      s.bmax = ws.bmax.as<uint32_t>();
+      s.part = ws.fpart.as<float2>();
+      s.mask = ws.cand.as<uint32_t>();
+      short_launch(ctx, s, batch);
+    }
+    if (!float_hint) {
+      ctx->prof.begin(st, kKMatchMerge);
+      hipLaunchKernelGGL(merge_kernel, dim3(S.row_wgs, batch), dim3(256), 0, st, a, S.nsplit);
+      ctx->prof.end(st);
+    }
+  };
+  run_pass(fa, F);
+  if (mutual) run_pass(ra, R);
+  VO_HIP_CHECK(hipGetLastError());
+}
+
+// The cross check's filter over best (batch, n0) with the reverse pass's rev (batch, n1)
+void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch, int n0, int n1) {
+  const int total = batch * n0;
+  if (total == 0) return;
+  hipLaunchKernelGGL(mutual_filter_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, d_best, d_rev,
+                     n0, n1, total);
   VO_HIP_CHECK(hipGetLastError());
 }
 
@@ -874,3 +988,4 @@ void compact_pairs(vo_ctx* ctx, const int32_t* d_best, int n0, int32_t* d_pairs,
 }
 
 }  // namespace vo
+

@@ -19,6 +19,9 @@
 // ranking the candidates by their exact fp32 chains reproduces the oracle.  Candidates
 // are recorded as bit masks (one 32-bit word per lane and 64-column chunk), so the set is
 // complete whatever its size, and the re-rank is deterministic.
+// Top-1 (the cross check's reverse pass, roles swapped): with m1 the smallest A of the row, the
+// smallest F is at most m1 + E, and every column whose F does not exceed it has A <= m1 + 2E:
+// the candidate set {i' : A <= m1 + 2E} holds every row the exact nearest can be (ties included).
 //
 // Kernels (one call, every launch exits at once unless the call's descriptors took the
 // float path -- pack_kernel's device-side flag -- and are finite, dim <= 256):
@@ -185,7 +188,8 @@ __global__ __launch_bounds__(256) void fpack_kernel(ShortArgs p, int a_wgs, int 
 // 16-column tile: B fragments from LDS, KS MFMAs per M tile, then per (row, column)
 // A' = |b'|^2 - 2 a'.b' and PASS 1: running top-2 (v_min_f32 + v_med3_f32), PASS 2: the
 // candidate test.
-template <int PASS, int KS>
+// TOP1 (PASS 1 of a top-1 call): the running minimum alone, one v_min_f32 per pair.
+template <int PASS, int KS, bool TOP1 = false>
 __global__ __launch_bounds__(256) void fsweep_kernel(ShortArgs p) {
   if (!short_active(p)) return;
   constexpr int Dp = 32 * KS;
@@ -238,7 +242,7 @@ __global__ __launch_bounds__(256) void fsweep_kernel(ShortArgs p) {
         }
         const float ra = p.ra[(long)b * p.n0_pad + row] + bm;
         // +inf when the row has < 2 columns; padding rows take nothing
-        thr[mt][r] = row < p.n0 ? a2 + 2.0f * kShortC * ra * ra : -__builtin_huge_valf();
+        thr[mt][r] = row < p.n0 ? (p.top1 ? a1 : a2) + 2.0f * kShortC * ra * ra : -__builtin_huge_valf();
       }
   }
 
@@ -303,7 +307,7 @@ __global__ __launch_bounds__(256) void fsweep_kernel(ShortArgs p) {
           for (int r = 0; r < 4; ++r) {
             const float v = fmaf(-2.0f, acc[u][mt][r], nc);
             if (PASS == 1) {
-              m2[mt][r] = med3_f32(m1[mt][r], m2[mt][r], v);
+              if constexpr (!TOP1) m2[mt][r] = med3_f32(m1[mt][r], m2[mt][r], v);
               m1[mt][r] = min_f32(m1[mt][r], v);
             } else {
               // row 16 mt + 4 g + r (g = lane >> 4), column cb + 16 u + (lane & 15)
@@ -331,10 +335,21 @@ __global__ __launch_bounds__(256) void fsweep_kernel(ShortArgs p) {
     M2 = med3_f32(M1, b1, fminf(M2, b2));                                                              \
     M1 = fminf(M1, b1);                                                                                \
   }
-        VO_TOP2_STEP(0x121)
-        VO_TOP2_STEP(0x122)
-        VO_TOP2_STEP(0x124)
-        VO_TOP2_STEP(0x128)
+#define VO_TOP1_STEP(CTRL) \
+  M1 = fminf(M1, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(M1), CTRL, 0xF, 0xF, false)));
+        if constexpr (TOP1) {
+          VO_TOP1_STEP(0x121)
+          VO_TOP1_STEP(0x122)
+          VO_TOP1_STEP(0x124)
+          VO_TOP1_STEP(0x128)
+          M2 = __builtin_huge_valf();
+        } else {
+          VO_TOP2_STEP(0x121)
+          VO_TOP2_STEP(0x122)
+          VO_TOP2_STEP(0x124)
+          VO_TOP2_STEP(0x128)
+        }
+#undef VO_TOP1_STEP
 #undef VO_TOP2_STEP
         if ((lane & 15) == 0) {
           const int row = rowbase + 16 * mt + 4 * (lane >> 4) + r;
@@ -679,6 +694,7 @@ __global__ __launch_bounds__(256, VO_RERANK_WGS) void frerank_kernel(ShortArgs p
   const int j2 = k2 == ~0ull ? -1 : (int)(uint32_t)k2;
   const long o = (long)b * p.n0 + row;
   if (p.best) p.best[o] = (j2 >= 0 && (double)s1 < p.ratio * (double)s2) ? j1 : -1;
+  if (p.rev) p.rev[o] = j1;
   if (p.idx2) {
     p.idx2[2 * o] = j1;
     p.idx2[2 * o + 1] = j2;
@@ -717,7 +733,8 @@ void short_launch(vo_ctx* ctx, ShortArgs& a, int batch) {
   switch (a.Dp / 32) {
 #define VO_SWEEPS(KS)                                                                \
   case KS:                                                                           \
-    hipLaunchKernelGGL((fsweep_kernel<1, KS>), grid, dim3(256), 0, st, a);           \
+    if (a.top1) hipLaunchKernelGGL((fsweep_kernel<1, KS, true>), grid, dim3(256), 0, st, a); \
+    else hipLaunchKernelGGL((fsweep_kernel<1, KS>), grid, dim3(256), 0, st, a);      \
     hipLaunchKernelGGL((fsweep_kernel<2, KS>), grid, dim3(256), 0, st, a);           \
     break;
     VO_SWEEPS(1)

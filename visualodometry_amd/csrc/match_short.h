@@ -20,11 +20,13 @@ struct ShortArgs {
   long a_bstride, b_bstride;
   const uint32_t* flag;  // [0] == gen: not SIFT integers; [1] == gen: a non-finite value
   uint32_t gen;
+  int top1;              // the cross check's reverse pass: only the nearest column is wanted
   int forced;            // float hint: no int8 pack ran; fpack itself flags non-finite values
   double ratio;
   int32_t* best;
   int32_t* idx2;
   float* dist2;
+  int32_t* rev;          // the cross check's reverse pass: (batch, n0) nearest column, -1 = none
 };
 
 // words between two frame pairs' max |b| counters: one 128-byte line each (the fpack

@@ -15,6 +15,7 @@ struct MatchWorkspace {
   DevBuf colconst;  // uint32 per train column (see match.hip)
   DevBuf partial;   // per (split, row) top-2 partials
   DevBuf best;      // int32 (batch, n0) best train index or -1
+  DevBuf rev;       // cross check: int32 (batch, n1) nearest query row of each train row
   DevBuf top2;      // int32 (n0, 2) + float (n0, 2)
   DevBuf pairs;     // int32 (n0, 2) compacted pairs + count
   DevBuf flag;      // uint32: == gen when this call's descriptors are not 0..255 integers
@@ -38,6 +39,7 @@ struct MatchQueryCache {
   DevBuf des;    // host sources: the query's float32 rows on the device
   DevBuf q8;     // packed int8 (a - 128) rows (n0_pad x Dp)
   DevBuf norms;  // int32 squared norms
+  DevBuf colconst;  // uint32 column constants (the cross check's reverse pass takes these rows as columns)
   DevBuf flag;   // [0] 1 = a value is not a 0..255 integer, [1] 1 = a value is not finite
   uint64_t tag = 0;
   const void* src = nullptr;
@@ -139,7 +141,8 @@ namespace vo {
 // Matcher entry points (match.hip).
 void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0,
                int n1, int dim, double ratio, int32_t* d_best, int32_t* d_idx2,
-               float* d_dist2, const MatchQueryCache* qc = nullptr);
+               float* d_dist2, const MatchQueryCache* qc = nullptr, int32_t* d_rev = nullptr);
+void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch, int n0, int n1);
 void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc);
 void compact_pairs(vo_ctx* ctx, const int32_t* d_best, int n0, int32_t* d_pairs,
                    int32_t* d_count);

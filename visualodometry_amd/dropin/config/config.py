@@ -51,6 +51,9 @@ class VOConfig:
     ba_lambda: float = 1.0  # fixed Levenberg damping (identical in oracle and kernel)
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
+    match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)
+    superpoint_bf_match: bool = False  # SuperPoint: brute-force ratio + cross-check matcher instead of LightGlue
+    superpoint_bf_ratio: float = 0.75  # its ratio (frontend.py:104's value; no accuracy measured for SuperPoint)
     triangulate_on_gpu: bool = True  # triangulate_points on the MI355X (DLT + filters)
     pnp_on_gpu: bool = True  # cv2.solvePnPRansac of the tracking step on the MI355X
     map_store_arrays: bool = True  # map_points as an id-indexed array store (MapStore)
@@ -84,14 +87,17 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
 
     ``src/main.py`` calls ``get_config(dataset)`` only (``main.py:54``), so two
     environment switches reach the back end without touching it:
-    ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``) and ``VO_AMD_BA=1``
-    (``ba_enabled``).  Unset, the result equals the reference's.
+    ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``), ``VO_AMD_BA=1``
+    (``ba_enabled``) and ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``).  Unset, the
+    result equals the reference's.
     """
     cfg = VOConfig()
     if extractor_type is None:
         extractor_type = os.environ.get("VO_AMD_EXTRACTOR") or None
     if os.environ.get("VO_AMD_BA", "0") not in ("", "0"):
         cfg.ba_enabled = True
+    if os.environ.get("VO_AMD_SP_BF", "0") not in ("", "0"):
+        cfg.superpoint_bf_match = True
     if extractor_type is not None:
         cfg.extractor_type = extractor_type
     base, sift = _DATASET_OVERRIDES.get(dataset, ({}, {}))

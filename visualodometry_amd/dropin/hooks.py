@@ -304,7 +304,17 @@ def _wrap_match_frames(orig):
             # which other users of the context may rely on, is restored afterwards)
             # feats0 is the keyframe's (vo.py:64-65): its packed rows stay cached across frames
             return matcher.match_knn2_ratio(feats0["descriptors"], feats1["descriptors"],
-                                            kind=matcher.DESC_SIFT, cache_query=True)
+                                            kind=matcher.DESC_SIFT, cache_query=True,
+                                            cross_check=bool(getattr(self.conf, "match_cross_check", False)))
+        if getattr(self.conf, "extractor_type", None) == "superpoint" and \
+                getattr(self.conf, "superpoint_bf_match", False):
+            # BASELINE config 5: brute force in place of LightGlue (frontend.py:77-84).  The VO loop
+            # indexes keyframe["ids"][ref_indices] (vo.py:66,121), so the pairs must be one-to-one
+            # as LightGlue's are: ratio test + cross check.  The dicts' (1, N, 256) CUDA tensors
+            # are read in place; the result is the (M, 2) int64 array that branch returns
+            return matcher.match_knn2_ratio(feats0["descriptors"], feats1["descriptors"],
+                                            ratio=float(getattr(self.conf, "superpoint_bf_ratio", 0.75)),
+                                            kind=matcher.DESC_FLOAT, cache_query=True, cross_check=True)
         return orig(self, feats0, feats1)
 
     match_frames._vo_amd_wrapped = orig

@@ -62,7 +62,8 @@ def _tensor_2d(d):
 
 
 def match_knn2_ratio(des0, des1, ratio: float = RATIO_THRESH, ctx: _lib.Context | None = None,
-                     kind: int | None = None, cache_query: bool = False) -> np.ndarray:
+                     kind: int | None = None, cache_query: bool = False,
+                     cross_check: bool = False) -> np.ndarray:
     """Ratio-test matches as an ``int64`` array ``(M, 2)`` of (query, train), ascending query.
 
     ``kind`` (``DESC_SIFT`` / ``DESC_FLOAT``) is a hint for this call only: the context's own
@@ -71,7 +72,12 @@ def match_knn2_ratio(des0, des1, ratio: float = RATIO_THRESH, ctx: _lib.Context 
     ``cache_query``: ``des0`` is the keyframe side the reference matches every frame against
     (``vo.py:64-65``): the library keeps its device copy and packed rows across calls while the
     same unmodified torch tensor comes back.  Torch tensors already on the GPU are read in place
-    (``vo_match_knn2_ratio_dev``: no descriptor crosses PCIe); results never depend on either."""
+    (``vo_match_knn2_ratio_dev``: no descriptor crosses PCIe); results never depend on either.
+
+    ``cross_check``: a kept pair ``(i, j)`` survives only if ``i`` is also the nearest query row
+    of train row ``j`` (OpenCV's ``BFMatcher(crossCheck=True)`` rule on top of the ratio test,
+    equal distances keeping the lower query index; ``vo_match_mutual``).  The pairs are then
+    one-to-one.  ``False`` takes exactly the calls above."""
     ctx = ctx or _lib.context()
     dev = None if getattr(ctx, "_foreign_tensors", False) else _gpu_tensors(des0, des1, ctx)
     if dev is not None:
@@ -92,7 +98,23 @@ def match_knn2_ratio(des0, des1, ratio: float = RATIO_THRESH, ctx: _lib.Context 
     if scoped:
         check(ctx.lib.vo_match_hint(ctx.handle, int(kind)), "vo_match_hint")
     try:
-        if dev is not None:
+        if cross_check:
+            if dev is not None:
+                import torch
+
+                torch.cuda.current_stream(a.device).synchronize()  # the tensors' producer is done
+                p0, p1, flags = a.data_ptr(), b.data_ptr(), _lib.VO_MATCH_DEVICE_PTRS
+            else:
+                p0, p1, flags = a.ctypes.data, b.ctypes.data, 0
+            rc = ctx.lib.vo_match_mutual(
+                ctx.handle, C.c_void_p(p0), n0, C.c_uint64(tag), C.c_void_p(p1), n1, dim, float(ratio), flags,
+                ptr(out, C.c_int32), ptr(cnt, C.c_int32))
+            if dev is not None and rc == _lib.VO_ERR_ARG:
+                # as below: torch's device memory is not this library's HIP runtime's
+                ctx._foreign_tensors = True
+                return match_knn2_ratio(des0.detach().cpu(), des1.detach().cpu(), ratio, ctx, kind, False, True)
+            check(rc, "vo_match_mutual")
+        elif dev is not None:
             import torch
 
             torch.cuda.current_stream(a.device).synchronize()  # the tensors' producer is done
@@ -160,12 +182,14 @@ def match_knn2(des0, des1, ctx: _lib.Context | None = None):
 
 
 def match_batch_device(des0: _lib.DeviceArray, des1: _lib.DeviceArray, ratio: float = RATIO_THRESH,
-                       out: _lib.DeviceArray | None = None, ctx: _lib.Context | None = None):
+                       out: _lib.DeviceArray | None = None, ctx: _lib.Context | None = None,
+                       cross_check: bool = False):
     """Batched frame pairs already resident in HBM.
 
     ``des0`` (B, n0, D) and ``des1`` (B, n1, D) float32 :class:`DeviceArray`;
     returns the (B, n0) int32 :class:`DeviceArray` of kept train indices
     (-1 = rejected).  Enqueued on the library stream; call :func:`synchronize`.
+    ``cross_check`` as in :func:`match_knn2_ratio` (``vo_match_mutual_batch_async``).
     """
     if len(des0.shape) != 3 or len(des1.shape) != 3 or des0.shape[0] != des1.shape[0] \
             or des0.shape[2] != des1.shape[2]:
@@ -176,12 +200,13 @@ def match_batch_device(des0: _lib.DeviceArray, des1: _lib.DeviceArray, ratio: fl
     ctx = ctx or des0.ctx
     if out is None:
         out = _lib.DeviceArray(ctx, (B, n0), np.int32)
+    name = "vo_match_mutual_batch_async" if cross_check else "vo_match_batch_async"
     check(
-        ctx.lib.vo_match_batch_async(
+        getattr(ctx.lib, name)(
             ctx.handle, C.c_void_p(des0.ptr), C.c_void_p(des1.ptr), B, n0, des1.shape[1], D,
             float(ratio), C.c_void_p(out.ptr),
         ),
-        "vo_match_batch_async",
+        name,
     )
     return out
 
