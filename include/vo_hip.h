@@ -248,8 +248,10 @@ int vo_ba_debug_stamps(vo_ctx* ctx, uint64_t* out, int n);
  *      retainBest, compaction), 15 sift_desc, 16 match_rerank (the float path's exact
  *      re-rank; before it had an id of its own it was timed under match_merge),
  *      17 pnp_decide, 18 pnp_hyp_tail, 19 pnp_score_tail (large batches: the replay after
- *      the first hypotheses of every frame, then the rest for the frames still looping). */
-#define VO_PROFILE_KERNELS 20
+ *      the first hypotheses of every frame, then the rest for the frames still looping),
+ *      20 ess_hyp, 21 ess_score (both: the first slice and the rest), 22 ess_decide,
+ *      23 ess_final, 24 ess_pose (essential-matrix initialisation). */
+#define VO_PROFILE_KERNELS 25
 int vo_profile_enable(vo_ctx* ctx, int on);
 int vo_profile_read(vo_ctx* ctx, double* ms_out, int64_t* counts_out);
 
@@ -324,6 +326,23 @@ int vo_pnp_ransac_batch_async(vo_ctx* ctx, const float* d_objpts, const float* d
 /* Host only: the RANSAC subsets the cv::RNG((uint64)-1) stream gives for `count` points
  * (iterations x 5 int32), for parity tests. */
 int vo_pnp_subsets(int count, int iterations, int32_t* out);
+
+/* ---- Essential-matrix initialisation (reference src/modules/vo.py:87-101) -- */
+/* Replaces cv2.findEssentialMat(pts1, pts2, K, method=RANSAC, prob, threshold): five-point
+ * RANSAC over the cv::RNG((uint64)-1) subsets vo_pnp_subsets draws, Sampson error, OpenCV's
+ * loop bookkeeping, no refinement.  Host arrays, synchronous.  pts1/pts2: n x 2 float32 pixels,
+ * K row-major 3x3.  E_out: row-major, unit Frobenius norm (zero on failure); mask_out[n]: 1 for
+ * the inliers of E.  n < 5 or no model with more than 4 inliers: *success_out = 0, mask zero.
+ * The models of a subset are tried in ascending order of the eliminated unknown (DESIGN.md
+ * §Essential); for n == 5 the first model is returned, not OpenCV's stack of all of them. */
+int vo_essential_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int n, const double* K, int max_iters,
+                        double threshold, double prob, double* E_out, uint8_t* mask_out, int32_t* success_out,
+                        int32_t* inliers_out);
+/* Replaces cv2.recoverPose(E, pts1, pts2, K): the first of [R1|t] [R2|t] [R1|-t] [R2|-t] with the
+ * most triangulated points in front of both cameras and nearer than distance_thresh (OpenCV:
+ * 50).  R_out row-major, t_out unit, mask_out[n] 0/1, *good_out the count. */
+int vo_recover_pose(vo_ctx* ctx, const double* E, const float* pts1, const float* pts2, int n, const double* K,
+                    double distance_thresh, double* R_out, double* t_out, uint8_t* mask_out, int32_t* good_out);
 
 /* ---- SIFT keypoint detection (the extrema stage) ----- */
 /* Replaces the keypoint detection of cv2.SIFT_create(nfeatures, contrastThreshold,

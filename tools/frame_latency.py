@@ -13,6 +13,9 @@ GPU as the reference's frontend does (frontend.py:3, :66-67): what process_frame
   pnp                 pnp_ransac, 1000 correspondences (vo.py:135-141)
   match_mutual_gpu_cached   match_frames hook with match_cross_check on, 4000 x 4000 x 128, keyframe cached
   superpoint_bf_match       match_frames hook, config 5's brute-force route, 2048 x 2048 x 256 GPU tensors
+  essential_init      findEssentialMat + recoverPose through the cv2-signature wrappers, 1500
+                      correspondences with 20 % outliers (vo.py:87-101; about what the ratio test
+                      leaves of 4000 SIFT keypoints), with the min / max of its repeats
   match_forward / match_swapped / match_composed _<shape>   the forward-only calls the cross check can be
                       composed from (forward, the swapped call, both plus a host-side intersection),
                       each with the min / max of its own repeats (_minmax_ms)
@@ -30,9 +33,10 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 dev = torch.device("cuda")
 torch.ones(8, device=dev).sum().item()  # torch's HIP runtime first
 
-from visualodometry_amd import _lib, matcher, pnp, sift  # noqa: E402
+from visualodometry_amd import _lib, essential, matcher, pnp, sift  # noqa: E402
 from visualodometry_amd.dropin import hooks  # noqa: E402
-from visualodometry_amd.synthetic import pnp_case, sift_like_pair, sift_scene, superpoint_like_pair  # noqa: E402
+from visualodometry_amd.synthetic import (pnp_case, sift_like_pair, sift_scene, superpoint_like_pair,  # noqa: E402
+                                          two_view_case)
 
 
 def timed(fn, reps=20, warm=3):
@@ -146,4 +150,20 @@ for _ in range(10):
 prof = _lib.profile_read(ctx)
 _lib.profile_enable(ctx, False)
 out["pnp_kernel_us"] = {k: round(v[0] / v[1] * 1e3, 2) for k, v in prof.items()}
+e1, e2, Ke, _, _, _ = two_view_case(1500, 7, noise_px=0.3, outlier_frac=0.2)
+
+
+def essential_init():  # vo.py:87-96
+    E, _ = essential.findEssentialMat(e1, e2, Ke, method=essential.RANSAC, prob=0.999, threshold=1.0, ctx=ctx)
+    return essential.recoverPose(E, e1, e2, Ke, ctx=ctx)
+
+
+spread("essential_init_ms", essential_init)
+out["essential_init_good"] = int(essential_init()[0])
+_lib.profile_enable(ctx, True)
+for _ in range(10):
+    essential_init()
+prof = _lib.profile_read(ctx)
+_lib.profile_enable(ctx, False)
+out["essential_init_kernel_us"] = {k: round(v[0] / 10 * 1e3, 2) for k, v in prof.items()}  # per call
 print(json.dumps(out))

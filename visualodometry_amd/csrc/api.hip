@@ -408,6 +408,28 @@ int vo_pnp_ransac_batch_async(vo_ctx* ctx, const float* d_objpts, const float* d
   });
 }
 
+int vo_essential_ransac(vo_ctx* ctx, const float* pts1, const float* pts2, int n, const double* K, int max_iters,
+                        double threshold, double prob, double* E_out, uint8_t* mask_out, int32_t* success_out,
+                        int32_t* inliers_out) {
+  return guarded([&] {
+    vo::bind(ctx);
+    VO_REQUIRE(K && n >= 0 && E_out && success_out && inliers_out, VO_ERR_ARG, "vo_essential_ransac: bad arguments");
+    VO_REQUIRE(n == 0 || (pts1 && pts2 && mask_out), VO_ERR_ARG, "vo_essential_ransac: null arrays");
+    vo::essential_ransac_host(ctx, pts1, pts2, n, K, max_iters, threshold, prob, E_out, mask_out, success_out,
+                              inliers_out);
+  });
+}
+
+int vo_recover_pose(vo_ctx* ctx, const double* E, const float* pts1, const float* pts2, int n, const double* K,
+                    double distance_thresh, double* R_out, double* t_out, uint8_t* mask_out, int32_t* good_out) {
+  return guarded([&] {
+    vo::bind(ctx);
+    VO_REQUIRE(E && K && n >= 0 && R_out && t_out && good_out, VO_ERR_ARG, "vo_recover_pose: bad arguments");
+    VO_REQUIRE(n == 0 || (pts1 && pts2 && mask_out), VO_ERR_ARG, "vo_recover_pose: null arrays");
+    vo::recover_pose_host(ctx, E, pts1, pts2, n, K, distance_thresh, R_out, t_out, mask_out, good_out);
+  });
+}
+
 int vo_sift_detect(vo_ctx* ctx, const uint8_t* img, int h, int w, double contrast, double edge, double sigma,
                    int n_layers, int capacity, float* kp_f, int32_t* kp_i, int32_t* count) {
   return guarded([&] {

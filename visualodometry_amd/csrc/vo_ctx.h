@@ -62,6 +62,18 @@ struct PnpWorkspace {
   int last_h1 = 0;  // hypotheses solved for every frame by the last call (pnp_run)
 };
 
+// Essential-matrix workspace (essential.hip): RANSAC subsets cached per (n, max_iters).
+struct EssWorkspace {
+  DevBuf q;       // double (n, 4) normalised correspondences
+  DevBuf sub;     // int32 (H, 5) subsets
+  DevBuf models;  // double (H, 10, 9)
+  DevBuf counts;  // int32 (H, 10) inlier counts, (H) model counts, the go-on flag
+  DevBuf flags;   // uint8 (n, 4) recoverPose: point passes under candidate
+  DevBuf stage;   // host-call staging: points, outputs
+  HostBuf hstage; // its page-locked mirror
+  int sub_n = -1, sub_H = -1;  // what the cached subsets were made for
+};
+
 // SIFT detection workspace (sift.hip): Gaussian and DoG pyramids of a batch.
 struct SiftWorkspace {
   DevBuf g, d;     // float pyramids (pitched, all octaves)
@@ -97,7 +109,8 @@ struct Comm;      // ba.hip (RCCL communicator)
 enum KernelId {
   kKBaLin = 0, kKBaReduce, kKBaSolve, kKMatchPack, kKMatchI8, kKMatchF32, kKMatchMerge,
   kKTriangulate, kKPnpHyp, kKPnpScore, kKPnpFinal, kKSiftPyramid, kKSiftExtrema, kKSiftOrient, kKSiftSelect,
-  kKSiftDesc, kKMatchRerank, kKPnpDecide, kKPnpHypTail, kKPnpScoreTail, kKCount
+  kKSiftDesc, kKMatchRerank, kKPnpDecide, kKPnpHypTail, kKPnpScoreTail, kKEssHyp, kKEssScore, kKEssDecide, kKEssFinal,
+  kKEssPose, kKCount
 };
 
 // HIP-event timing of individual kernels on the context stream (off by default).
@@ -123,6 +136,7 @@ struct vo_ctx {
   vo::MatchWorkspace match;
   vo::MatchQueryCache match_q;
   vo::PnpWorkspace pnp;
+  vo::EssWorkspace ess;
   vo::SiftWorkspace sift;
   vo::Profiler prof;
   std::unique_ptr<vo::BAEngine> ba;
@@ -155,6 +169,12 @@ void pnp_run(vo_ctx* ctx, const float* d_X, const float* d_uv, const int32_t* of
              const double* K, int iterations, double reproj_err, double confidence, double* d_pose,
              uint8_t* d_mask, int32_t* d_status);
 void pnp_subsets(int count, int iters, int32_t* out);
+// Essential-matrix RANSAC and recoverPose (essential.hip): host arrays, synchronous.
+void essential_ransac_host(vo_ctx* ctx, const float* pts1, const float* pts2, int n, const double* K, int max_iters,
+                           double threshold, double prob, double* E_out, uint8_t* mask_out, int32_t* success_out,
+                           int32_t* inliers_out);
+void recover_pose_host(vo_ctx* ctx, const double* E, const float* pts1, const float* pts2, int n, const double* K,
+                       double distance_thresh, double* R_out, double* t_out, uint8_t* mask_out, int32_t* good_out);
 // SIFT detection (sift.hip): device images, device keypoint outputs (unsorted).
 void sift_run(vo_ctx* ctx, const uint8_t* d_img, int batch, int h, int w, double contrast, double edge,
               double sigma, int n_layers, int capacity, float* d_kpf, int32_t* d_kpi, int32_t* d_count,

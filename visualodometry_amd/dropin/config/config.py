@@ -56,6 +56,7 @@ class VOConfig:
     superpoint_bf_ratio: float = 0.75  # its ratio (frontend.py:104's value; no accuracy measured for SuperPoint)
     triangulate_on_gpu: bool = True  # triangulate_points on the MI355X (DLT + filters)
     pnp_on_gpu: bool = True  # cv2.solvePnPRansac of the tracking step on the MI355X
+    init_on_gpu: bool = False  # cv2.findEssentialMat + recoverPose of the initialisation on the MI355X
     map_store_arrays: bool = True  # map_points as an id-indexed array store (MapStore)
 
 
@@ -88,8 +89,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
     ``src/main.py`` calls ``get_config(dataset)`` only (``main.py:54``), so two
     environment switches reach the back end without touching it:
     ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``), ``VO_AMD_BA=1``
-    (``ba_enabled``) and ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``).  Unset, the
-    result equals the reference's.
+    (``ba_enabled``), ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``) and ``VO_AMD_INIT=1``
+    (``init_on_gpu``).  Unset, the result equals the reference's.
     """
     cfg = VOConfig()
     if extractor_type is None:
@@ -98,6 +99,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
         cfg.ba_enabled = True
     if os.environ.get("VO_AMD_SP_BF", "0") not in ("", "0"):
         cfg.superpoint_bf_match = True
+    if os.environ.get("VO_AMD_INIT", "0") not in ("", "0"):
+        cfg.init_on_gpu = True
     if extractor_type is not None:
         cfg.extractor_type = extractor_type
     base, sift = _DATASET_OVERRIDES.get(dataset, ({}, {}))

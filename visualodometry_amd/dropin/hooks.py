@@ -217,6 +217,7 @@ def _wrap_init(orig):
     def __init__(self, *args, **kw):  # VisualOdometry(K, config), vo.py:9
         orig(self, *args, **kw)
         _PNP_ON_GPU[0] = bool(getattr(self.cfg, "pnp_on_gpu", True))
+        _INIT_ON_GPU[0] = bool(getattr(self.cfg, "init_on_gpu", False))
         _use_map_store(self)
         if getattr(self.cfg, "ba_enabled", False):
             # the BA context pre-sized for a full window (ba_window keyframes, the map's
@@ -253,6 +254,7 @@ def _wrap_reset(orig):
 
 
 _PNP_ON_GPU = [True]  # set from the VO config at construction (cfg.pnp_on_gpu)
+_INIT_ON_GPU = [False]  # likewise cfg.init_on_gpu (findEssentialMat + recoverPose, vo.py:87-101)
 
 
 def _wrap_frontend_init(orig):
@@ -335,11 +337,13 @@ def _wrap_triangulate(orig):
 
 class Cv2Proxy:
     """Stands in for the ``cv2`` module inside ``modules.vo``: ``solvePnPRansac`` runs on
-    the MI355X, every other attribute is the real cv2's."""
+    the MI355X, and so do ``findEssentialMat`` and ``recoverPose`` of the initialisation
+    (``vo.py:87-101``) when ``init_enabled()``; every other attribute is the real cv2's."""
 
-    def __init__(self, real, enabled=lambda: True):
+    def __init__(self, real, enabled=lambda: True, init_enabled=lambda: False):
         self._vo_amd_real = real
         self._enabled = enabled
+        self._init_enabled = init_enabled
 
     def __getattr__(self, name):
         return getattr(self._vo_amd_real, name)
@@ -350,6 +354,22 @@ class Cv2Proxy:
 
             return pnp.solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, *args, **kw)
         return self._vo_amd_real.solvePnPRansac(objectPoints, imagePoints, cameraMatrix, distCoeffs, *args, **kw)
+
+    def findEssentialMat(self, points1, points2, *args, **kw):
+        if self._init_enabled():
+            from .. import essential
+
+            if kw.get("method") == getattr(self._vo_amd_real, "RANSAC", essential.RANSAC):
+                kw["method"] = essential.RANSAC
+            return essential.findEssentialMat(points1, points2, *args, **kw)
+        return self._vo_amd_real.findEssentialMat(points1, points2, *args, **kw)
+
+    def recoverPose(self, E, points1, points2, *args, **kw):
+        if self._init_enabled():
+            from .. import essential
+
+            return essential.recoverPose(E, points1, points2, *args, **kw)
+        return self._vo_amd_real.recoverPose(E, points1, points2, *args, **kw)
 
 
 def install(frontend_cls=None, vo_cls=None) -> None:
@@ -387,4 +407,4 @@ def install(frontend_cls=None, vo_cls=None) -> None:
     vo_mod = sys.modules.get(vo_cls.__module__)
     real_cv2 = getattr(vo_mod, "cv2", None) if vo_mod is not None else None
     if real_cv2 is not None and not isinstance(real_cv2, Cv2Proxy):
-        vo_mod.cv2 = Cv2Proxy(real_cv2, lambda: _PNP_ON_GPU[0])
+        vo_mod.cv2 = Cv2Proxy(real_cv2, lambda: _PNP_ON_GPU[0], lambda: _INIT_ON_GPU[0])

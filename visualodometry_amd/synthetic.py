@@ -329,6 +329,59 @@ def triangulation_case(n: int, seed: int, noise_px: float = 0.5, outlier_frac: f
     return T_cw1, T_cw2, p1.astype(np.float32), p2.astype(np.float32), K, X, kind
 
 
+def two_view_case(n: int, seed: int, noise_px: float = 0.3, outlier_frac: float = 0.2, motion: str = "forward"):
+    """An initialisation input of the reference's shape (``vo.py:87-101``): ``n`` matched
+    keypoints (float32) of two views of points 5-50 m in front of both cameras, KITTI K,
+    :func:`triangulation_case`'s geometry without behind-camera points.  ``motion``:
+    ``"forward"`` the KITTI-like 1 m advance with a small yaw, ``"sideways"`` a 1 m lateral
+    baseline, ``"turn"`` the advance plus about 0.1 rad of yaw.  A fraction of the
+    correspondences are gross outliers (camera-2 point moved 30-100 px across its epipolar line).
+
+    Returns (pts1 (n,2) f32, pts2 (n,2) f32, K, R (3,3), t (3,) unit, is_outlier (n,) bool) with
+    ``X2 = R X1 + t * baseline``."""
+    if motion not in ("forward", "sideways", "turn"):
+        raise ValueError(f"two_view_case: unknown motion {motion!r}")
+    rng = np.random.default_rng(seed)
+    K = KITTI_K.copy()
+    yaw = rng.normal(0.0, 0.02) + (0.1 if motion == "turn" else 0.0)
+    Rwc2 = so3_exp(np.array([0.0, yaw, 0.0]))
+    small = np.array([rng.normal(0, 0.05), rng.normal(0, 0.02)])
+    C2 = np.array([1.0, small[1], small[0]]) if motion == "sideways" else np.array([small[0], small[1], 1.0])
+    R = Rwc2.T  # camera 1 is the world frame: X2 = R (X1 - C2)
+    t = -R @ C2
+    out = np.zeros(n, dtype=bool)
+    out[rng.permutation(n)[: int(outlier_frac * n)]] = True
+    e1 = K @ C2
+    e1 = e1[:2] / e1[2] if abs(e1[2]) > 0.5 else np.array([1e9, 1e9])  # sideways: epipole far outside
+    X = np.empty((n, 3))
+    filled = 0
+    while filled < n:
+        m = 4 * max(n, 1)
+        px = np.stack([rng.uniform(50, 1190, m), rng.uniform(30, 345, m)], 1)
+        depth = rng.uniform(5.0, 50.0, m)
+        Xc = np.linalg.solve(K, np.concatenate([px, np.ones((m, 1))], 1).T).T * depth[:, None]
+        z2 = ((Xc - C2) @ R.T)[:, 2]
+        # >= 150 px from the epipole of a forward motion (enough parallax), in front of camera 2
+        keep = (np.linalg.norm(px - e1, axis=1) > 150.0) & (z2 > 2.0) & (z2 < 49.0)
+        Xc = Xc[keep][: n - filled]
+        X[filled:filled + len(Xc)] = Xc
+        filled += len(Xc)
+
+    def proj(Xc):
+        q = (K @ Xc.T).T
+        return q[:, :2] / q[:, 2:3]
+
+    p1 = proj(X) + rng.normal(0, noise_px, (n, 2))
+    p2 = proj((X - C2) @ R.T) + rng.normal(0, noise_px, (n, 2))
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    Ki = np.linalg.inv(K)
+    lines = (Ki.T @ tx @ R @ Ki @ np.concatenate([p1, np.ones((n, 1))], 1).T).T
+    nrm = lines[:, :2] / np.linalg.norm(lines[:, :2], axis=1, keepdims=True)
+    d = rng.uniform(30, 100, n) * np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    p2[out] += (nrm * d[:, None])[out]
+    return p1.astype(np.float32), p2.astype(np.float32), K, R, t / np.linalg.norm(t), out
+
+
 def pnp_case(n: int, seed: int, noise_px: float = 0.3, outlier_frac: float = 0.25):
     """A tracking-step input of the reference's shape (``vo.py:129-141``): ``n`` map points
     (float32, as ``map_points`` holds them, ``vo.py:281``) seen by a camera with KITTI K
