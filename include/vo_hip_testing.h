@@ -70,6 +70,20 @@ int vo_pnp_testing_last_split(vo_ctx* ctx, int* h1, int* tail_frames);
  * check on one batch through both. */
 int vo_pnp_testing_group(vo_ctx* ctx, int mode);
 
+/* Test entry: the SIFT selection stage alone (what detectAndCompute runs between its orientation
+ * and descriptor kernels: sort keys, the batch-wide sort, then removeDuplicatedSorted +
+ * retainBest(nfeatures) + ordered compaction) on the caller's records, through the same helper,
+ * workspace and stream as the product path.  Host arrays: okp (batch, cap_img, 8) float32
+ * oriented-keypoint records in doubled-image units (x, y, size, angle, response, octave-word
+ * bits, 0, 0; x and y in [4.5, 32768)), counts (batch) records filled per image.  Outputs: sel
+ * (batch, cap_img) record indices b * cap_img + slot in output order, sel_count (batch) kept per
+ * image, or for a batch with a count above cap_img minus that count in its image (the other
+ * images' values are then unspecified).  batch 1..256, cap_img 1..131072; synchronous.  Real
+ * images almost never produce equal-(x, y) runs over two records or tied responses: the GPU
+ * tests build them. */
+int vo_sift_testing_select(vo_ctx* ctx, const float* okp, const int32_t* counts, int batch, int cap_img,
+                           int nfeatures, uint32_t* sel, int32_t* sel_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -557,6 +557,26 @@ def _sort_key(k):
     return (k["x"], k["y"], -k["size"], k["angle"], -k["response"], -k["octave"])
 
 
+def select_keypoints(kps: list, nfeatures: int) -> tuple:
+    """detectAndCompute's keypoint filtering: the sort by KeyPoint12_LessThan (Python's sort is
+    stable, as the comparator's final ``i < j``), removeDuplicatedSorted, retainBest(nfeatures)
+    (every keypoint tied with the nfeatures-th response stays).  kps: dicts with x, y, size,
+    angle, response, octave -> (the survivors in output order, their indices in ``kps``)."""
+    order = sorted(range(len(kps)), key=lambda i: _sort_key(kps[i]))
+    uniq = []
+    for i in order:  # removeDuplicatedSorted
+        k = kps[i]
+        if uniq:
+            p = kps[uniq[-1]]
+            if p["x"] == k["x"] and p["y"] == k["y"] and p["size"] == k["size"] and p["angle"] == k["angle"]:
+                continue
+        uniq.append(i)
+    if nfeatures > 0 and len(uniq) > nfeatures:  # retainBest
+        t = np.sort(np.array([kps[i]["response"] for i in uniq], _f))[::-1][nfeatures - 1]
+        uniq = [i for i in uniq if kps[i]["response"] >= t]
+    return [kps[i] for i in uniq], uniq
+
+
 def detect_and_compute(gray: np.ndarray, nfeatures: int = 0, contrast: float = 0.04, edge: float = 10.0,
                        sigma: float = 1.6, n_layers: int = 3, with_descriptors: bool = True) -> dict:
     """``SIFT_create(nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma)
@@ -576,16 +596,7 @@ def detect_and_compute(gray: np.ndarray, nfeatures: int = 0, contrast: float = 0
         for ang in orientation_peaks(hist, omax):
             kps.append(dict(x=_f(det["pt"][i, 0] * _f(2)), y=_f(det["pt"][i, 1] * _f(2)), size=size2, angle=ang,
                             response=_f(det["response"][i]), octave=word_pre, o=o, layer=layer))
-    kps.sort(key=_sort_key)
-    uniq = []
-    for k in kps:  # removeDuplicatedSorted
-        if uniq and (uniq[-1]["x"] == k["x"] and uniq[-1]["y"] == k["y"] and uniq[-1]["size"] == k["size"] and
-                     uniq[-1]["angle"] == k["angle"]):
-            continue
-        uniq.append(k)
-    if nfeatures > 0 and len(uniq) > nfeatures:  # retainBest
-        t = np.sort(np.array([k["response"] for k in uniq], _f))[::-1][nfeatures - 1]
-        uniq = [k for k in uniq if k["response"] >= t]
+    uniq, _ = select_keypoints(kps, nfeatures)
     N = len(uniq)
     desc = np.zeros((N, SIFT_DESCR_WIDTH ** 2 * SIFT_DESCR_HIST_BINS), _f)
     if with_descriptors:

@@ -111,6 +111,7 @@ SIGNATURES = {
     "vo_sift_detect_and_compute": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _I, _D, _D, _D, _I, _I, _P, _PF, _PI32]),
     "vo_sift_detect_and_compute_dev": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _I, _D, _D, _D, _I, _I, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "vo_sift_detect_and_compute_batch_async": (_I, [_P, _P, _I, _I, _I, _I, _D, _D, _D, _I, _I, _P, _P, _P]),
+    "vo_sift_testing_select": (_I, [_P, _PF, _PI32, _I, _I, _I, C.POINTER(C.c_uint32), _PI32]),
     "vo_comm_init": (_I, [_P, _I, _I, C.c_char_p]),
     "vo_comm_init_loopback": (_I, [_P, _I, _I, C.c_char_p]),
     "vo_ba_split_reduce": (_I, [_P, _I]),

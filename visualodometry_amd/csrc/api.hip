@@ -999,6 +999,17 @@ int vo_pnp_testing_last_split(vo_ctx* ctx, int* h1, int* tail_frames) {
   });
 }
 
+int vo_sift_testing_select(vo_ctx* ctx, const float* okp, const int32_t* counts, int batch, int cap_img,
+                           int nfeatures, uint32_t* sel, int32_t* sel_count) {
+  return guarded([&] {
+    VO_REQUIRE(ctx != nullptr, VO_ERR_ARG, "vo_sift_testing_select: null context");
+    VO_REQUIRE(okp && counts && sel && sel_count && nfeatures >= 0, VO_ERR_ARG,
+               "vo_sift_testing_select: bad arguments");
+    vo::bind(ctx);
+    vo::sift_testing_select(ctx, okp, counts, batch, cap_img, nfeatures, sel, sel_count);
+  });
+}
+
 int vo_comm_init_loopback(vo_ctx* ctx, int nranks, int rank, const char id[128]) {
   return guarded([&] {
     vo::bind(ctx);

@@ -933,6 +933,99 @@ ExpTab make_exp_tab() {
   return t;
 }
 
+// The workspace arrays of the stages after detection, for a batch at a per-image capacity.
+struct SiftBufs {
+  float* okp;                   // (batch, cap_img, kOkpFloats)
+  uint64_t *keys_in, *keys_out; // (batch * cap_img) each
+  uint32_t *vals_in, *vals_out, *sel, *resp;
+  int32_t *img_count, *sel_count;
+  int32_t* work;  // read only by the kernels after select (which zeros it); kCountStride ints
+};
+
+static SiftBufs sift_buffers(vo_ctx* ctx, int batch, int cap_img) {
+  SiftWorkspace& ws = ctx->sift;
+  const size_t slots = (size_t)batch * cap_img;
+  ws.okp.reserve(slots * kOkpFloats * sizeof(float));
+  ws.keys.reserve(slots * 2 * sizeof(uint64_t));
+  ws.vals.reserve(slots * 4 * sizeof(uint32_t));
+  ws.segs.reserve(((size_t)(kCountStride + 1) * batch + kCountStride) * sizeof(int32_t));
+  SiftBufs B;
+  B.okp = ws.okp.as<float>();
+  B.keys_in = ws.keys.as<uint64_t>();
+  B.keys_out = B.keys_in + slots;
+  B.vals_in = ws.vals.as<uint32_t>();
+  B.vals_out = B.vals_in + slots;
+  B.sel = B.vals_out + slots;
+  B.resp = B.sel + slots;
+  B.img_count = ws.segs.as<int32_t>();
+  B.sel_count = B.img_count + (size_t)batch * kCountStride;
+  B.work = B.sel_count + batch;
+  return B;
+}
+
+// The selection stage between orientation and descriptors (sift_describe, and the test entry
+// vo_sift_testing_select): sort keys of the oriented keypoints B.okp / B.img_count, the
+// batch-wide sort, then removeDuplicatedSorted + retainBest + compaction into B.sel / B.sel_count.
+static void sift_select_stage(vo_ctx* ctx, const SiftBufs& B, int batch, int cap_img, int nfeatures,
+                              const int32_t* cand_count, int cand_cap) {
+  SiftWorkspace& ws = ctx->sift;
+  const size_t slots = (size_t)batch * cap_img;
+  hipStream_t st = ctx->stream;
+  ctx->prof.begin(st, kKSiftSelect);
+  hipLaunchKernelGGL(sift_keys_kernel, dim3(ceil_div((int64_t)slots, 256)), dim3(256), 0, st, B.okp, B.img_count,
+                     cap_img, batch, B.keys_in, B.vals_in);
+  // image bits 54.. (ceil(log2(batch + 1)) of them; unused slots are all ones)
+  int img_bits = 1;
+  while ((1 << img_bits) <= batch) ++img_bits;
+  const unsigned end_bit = 54u + (unsigned)img_bits;
+  size_t tmp_bytes = 0;
+  VO_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, B.keys_in, B.keys_out, B.vals_in, B.vals_out, slots, 0u,
+                                         end_bit, st));
+  ws.sort_tmp.reserve(tmp_bytes);
+  VO_HIP_CHECK(rocprim::radix_sort_pairs(ws.sort_tmp.ptr, tmp_bytes, B.keys_in, B.keys_out, B.vals_in, B.vals_out,
+                                         slots, 0u, end_bit, st));
+  SelArgs sa;
+  sa.okp = B.okp;
+  sa.keys = B.keys_out;
+  sa.vals = B.vals_out;
+  sa.img_count = B.img_count;
+  sa.cand_count = cand_count;
+  sa.cand_cap = cand_cap;
+  sa.cap_img = cap_img;
+  sa.nfeatures = nfeatures;
+  sa.sel = B.sel;
+  sa.sel_count = B.sel_count;
+  sa.resp = B.resp;
+  sa.work = B.work;
+  hipLaunchKernelGGL(sift_select_kernel, dim3(batch), dim3(kSelThreads), 0, st, sa);
+  VO_HIP_CHECK(hipGetLastError());
+  ctx->prof.end(st);
+}
+
+// Test entry (vo_sift_testing_select): the selection stage alone on the caller's records.
+void sift_testing_select(vo_ctx* ctx, const float* okp, const int32_t* counts, int batch, int cap_img, int nfeatures,
+                         uint32_t* sel, int32_t* sel_count) {
+  VO_REQUIRE(batch >= 1 && batch <= kMaxBatch, VO_ERR_ARG, "vo_sift_testing_select: batch %d outside 1..%d", batch,
+             kMaxBatch);
+  VO_REQUIRE(cap_img >= 1 && cap_img <= kMaxCapImg, VO_ERR_ARG, "vo_sift_testing_select: capacity %d outside 1..%d",
+             cap_img, kMaxCapImg);
+  for (int b = 0; b < batch; ++b)
+    VO_REQUIRE(counts[b] >= 0, VO_ERR_ARG, "vo_sift_testing_select: counts[%d] = %d < 0", b, counts[b]);
+  const SiftBufs B = sift_buffers(ctx, batch, cap_img);
+  const size_t slots = (size_t)batch * cap_img;
+  hipStream_t st = ctx->stream;
+  std::vector<int32_t> ic((size_t)batch * kCountStride, 0);
+  for (int b = 0; b < batch; ++b) ic[(size_t)b * kCountStride] = counts[b];
+  int32_t* cand_count = B.work + 1;  // spare words after the work counter: no candidate overflow
+  VO_HIP_CHECK(hipMemcpyAsync(B.okp, okp, slots * kOkpFloats * sizeof(float), hipMemcpyHostToDevice, st));
+  VO_HIP_CHECK(hipMemcpyAsync(B.img_count, ic.data(), ic.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  VO_HIP_CHECK(hipMemsetAsync(cand_count, 0, sizeof(int32_t), st));
+  sift_select_stage(ctx, B, batch, cap_img, nfeatures, cand_count, (int)std::min<size_t>(slots, 1 << 24));
+  VO_HIP_CHECK(hipMemcpyAsync(sel, B.sel, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  VO_HIP_CHECK(hipMemcpyAsync(sel_count, B.sel_count, (size_t)batch * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  VO_HIP_CHECK(hipStreamSynchronize(st));
+}
+
 // Orientation, filtering and descriptors of the candidates sift_run left in the workspace.
 int sift_max_capacity() { return kMaxCapImg; }
 
@@ -961,22 +1054,12 @@ void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double si
     O.op[o] = (int)lay[5 + 5 * o];
     O.off[o] = lay[6 + 5 * o];
   }
-  SiftWorkspace& ws = ctx->sift;
-  const size_t slots = (size_t)batch * cap_img;
-  ws.okp.reserve(slots * kOkpFloats * sizeof(float));
-  ws.keys.reserve(slots * 2 * sizeof(uint64_t));
-  ws.vals.reserve(slots * 4 * sizeof(uint32_t));
-  ws.segs.reserve(((size_t)(kCountStride + 1) * batch + kCountStride) * sizeof(int32_t));
-  float* okp = ws.okp.as<float>();
-  uint64_t* keys_in = ws.keys.as<uint64_t>();
-  uint64_t* keys_out = keys_in + slots;
-  uint32_t* vals_in = ws.vals.as<uint32_t>();
-  uint32_t* vals_out = vals_in + slots;
-  uint32_t* sel = vals_out + slots;
-  uint32_t* resp = sel + slots;
-  int32_t* img_count = ws.segs.as<int32_t>();
-  int32_t* sel_count = img_count + (size_t)batch * kCountStride;
-  int32_t* work = sel_count + batch;  // read only by the kernels after select (which zeros it)
+  const SiftBufs B = sift_buffers(ctx, batch, cap_img);
+  float* okp = B.okp;
+  uint32_t* sel = B.sel;
+  int32_t* img_count = B.img_count;
+  int32_t* sel_count = B.sel_count;
+  int32_t* work = B.work;
   hipStream_t st = ctx->stream;
   const ExpTab tab = make_exp_tab();
 
@@ -999,35 +1082,7 @@ void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double si
   VO_HIP_CHECK(hipGetLastError());
   ctx->prof.end(st);
 
-  ctx->prof.begin(st, kKSiftSelect);
-  hipLaunchKernelGGL(sift_keys_kernel, dim3(ceil_div((int64_t)slots, 256)), dim3(256), 0, st, okp, img_count, cap_img,
-                     batch, keys_in, vals_in);
-  // image bits 54.. (ceil(log2(batch + 1)) of them; unused slots are all ones)
-  int img_bits = 1;
-  while ((1 << img_bits) <= batch) ++img_bits;
-  const unsigned end_bit = 54u + (unsigned)img_bits;
-  size_t tmp_bytes = 0;
-  VO_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in, keys_out, vals_in, vals_out, slots, 0u, end_bit,
-                                         st));
-  ws.sort_tmp.reserve(tmp_bytes);
-  VO_HIP_CHECK(rocprim::radix_sort_pairs(ws.sort_tmp.ptr, tmp_bytes, keys_in, keys_out, vals_in, vals_out, slots, 0u,
-                                         end_bit, st));
-  SelArgs sa;
-  sa.okp = okp;
-  sa.keys = keys_out;
-  sa.vals = vals_out;
-  sa.img_count = img_count;
-  sa.cand_count = cand_count;
-  sa.cand_cap = cand_cap;
-  sa.cap_img = cap_img;
-  sa.nfeatures = nfeatures;
-  sa.sel = sel;
-  sa.sel_count = sel_count;
-  sa.resp = resp;
-  sa.work = work;
-  hipLaunchKernelGGL(sift_select_kernel, dim3(batch), dim3(kSelThreads), 0, st, sa);
-  VO_HIP_CHECK(hipGetLastError());
-  ctx->prof.end(st);
+  sift_select_stage(ctx, B, batch, cap_img, nfeatures, cand_count, cand_cap);
 
   ctx->prof.begin(st, kKSiftDesc);
   DescArgs da;

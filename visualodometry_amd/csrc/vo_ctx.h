@@ -185,4 +185,7 @@ int sift_max_capacity();  // largest per-image keypoint capacity of sift_describ
 void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double sigma, int nfeatures, int cap_img,
                    const float* cand_f, const int32_t* cand_i, const int32_t* cand_count, int cand_cap,
                    const float* G, vo_sift_keypoint* d_kp, float* d_desc, int32_t* d_count);
+// sift_describe's selection stage alone on host records (test entry vo_sift_testing_select).
+void sift_testing_select(vo_ctx* ctx, const float* okp, const int32_t* counts, int batch, int cap_img, int nfeatures,
+                         uint32_t* sel, int32_t* sel_count);
 }  // namespace vo

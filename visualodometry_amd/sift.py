@@ -183,6 +183,26 @@ def detect_and_compute_device(d_imgs: _lib.DeviceArray, nfeatures: int, contrast
         "vo_sift_detect_and_compute_batch_async")
 
 
+def select_records(okp, counts, nfeatures: int, ctx: _lib.Context | None = None) -> tuple:
+    """Test entry ``vo_sift_testing_select``: detectAndCompute's selection stage (sort,
+    removeDuplicatedSorted, retainBest, compaction) on caller-made oriented-keypoint records.
+    okp (batch, cap_img, 8) float32, counts (batch,) records filled per image -> (sel (batch,
+    cap_img) uint32 record indices ``b * cap_img + slot`` in output order, sel_count (batch,)
+    int32: kept per image, or minus the count of an image that overflowed cap_img)."""
+    ctx = ctx or _lib.context()
+    okp = np.ascontiguousarray(okp, dtype=np.float32)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    if okp.ndim != 3 or okp.shape[2] != 8 or counts.shape != (okp.shape[0],):
+        raise ValueError("select_records: okp (batch, cap_img, 8) and counts (batch,) are expected")
+    batch, cap_img = okp.shape[:2]
+    sel = np.zeros((batch, cap_img), np.uint32)
+    sel_count = np.zeros(batch, np.int32)
+    check(ctx.lib.vo_sift_testing_select(ctx.handle, ptr(okp, C.c_float), ptr(counts, C.c_int32), batch, cap_img,
+                                         int(nfeatures), ptr(sel, C.c_uint32), ptr(sel_count, C.c_int32)),
+          "vo_sift_testing_select")
+    return sel, sel_count
+
+
 def unpack_device_keypoints(raw: np.ndarray) -> np.ndarray:
     """(…, 8) 32-bit words copied back from a device keypoint buffer -> KP_DTYPE records."""
     return np.ascontiguousarray(raw).view(KP_DTYPE).reshape(raw.shape[:-1])
