@@ -6,6 +6,8 @@
 #include <vector>
 
 #include "ba_band.h"
+#include "ba_comm.h"
+#include "ba_engine.h"
 #include "ba_plan.h"
 #include "vo_ctx.h"
 #include "../../include/vo_hip_testing.h"
@@ -67,20 +69,6 @@ void Profiler::read(double* ms, int64_t* counts) {
 Profiler::~Profiler() {
   for (hipEvent_t e : pool) (void)hipEventDestroy(e);
 }
-
-// ba.hip
-uint64_t ba_setup(vo_ctx*, const vo_ba_problem*);
-void ba_reserve(vo_ctx*, int, int, int64_t, int);
-void ba_check_session(vo_ctx*, uint64_t);
-void ba_set_state(vo_ctx*, const double*, const double*);
-void ba_get_state(vo_ctx*, double*, double*);
-int ba_run(vo_ctx*, int, double*, bool);
-int ba_gn_step(vo_ctx*, double*, double*, double*, double*);
-int ba_stats(vo_ctx*, int64_t*, int);
-int ba_stamps(vo_ctx*, uint64_t*, int);
-void comm_unique_id(char out[128]);
-void comm_init(vo_ctx*, int, int, const char*);
-void comm_init_loopback(vo_ctx*, int, int, const char*);
 
 namespace {
 

@@ -1,4 +1,4 @@
-// K3 for banded reduced camera systems (ba_band.hip), launched by the BA engine (ba.hip).
+// K3 for banded reduced camera systems (ba_band.hip), launched by the BA engine (ba_engine.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -45,7 +45,7 @@ struct BandLds {
 BandLds band_lds_layout(int F, const BandSplit& b, int n_poses, bool allow_split = true);
 BandTables band_tables(int F, const BandSplit& b, const BandLds& L);
 
-// K2 writes the reduced camera system in the banded layout (ba.hip, red_dst_): per side,
+// K2 writes the reduced camera system in the banded layout (ba_engine.hip, red_dst_): per side,
 // column v = band_col_stride(w) doubles -- block (v + q, v) of the side's coordinates
 // row-major at 36 q (the bottom side's blocks transposed), the rhs of row v at 36 (w + 1),
 // 6 zero doubles; top columns [0, m + s), then bottom columns [0, nb + s), then the cost.

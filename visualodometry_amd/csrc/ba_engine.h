@@ -1,0 +1,23 @@
+// Entry points of the BA engine (ba_engine.hip) used by api.hip; the engine is created in the
+// context on first use.
+#pragma once
+
+#include <cstdint>
+
+#include "vo_common.h"
+
+struct vo_ctx;
+
+namespace vo {
+
+uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p);
+void ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_fixed);
+void ba_check_session(vo_ctx* ctx, uint64_t session);
+void ba_set_state(vo_ctx* ctx, const double* poses, const double* pts);
+void ba_get_state(vo_ctx* ctx, double* poses, double* pts);
+int ba_run(vo_ctx* ctx, int iters, double* cost, bool sync);
+int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost);
+int ba_stats(vo_ctx* ctx, int64_t* out, int n);
+int ba_stamps(vo_ctx* ctx, uint64_t* out, int n);
+
+}  // namespace vo

@@ -1,0 +1,930 @@
+// The BA host engine: plans a window (ba_plan.h), keeps its device buffers and enqueues the
+// Gauss-Newton iterations on the context stream -- K1, K2 and the profile K3 through ba.hip's
+// launches (ba_kernels.h), the banded K3 (with K2 fused into its launch) through ba_band.hip's.
+// No kernel is defined here.
+#include "ba_engine.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ba_band.h"
+#include "ba_comm.h"
+#include "ba_kernels.h"
+#include "ba_plan.h"
+#include "vo_ctx.h"
+
+#ifndef VO_BA_FUSE
+#define VO_BA_FUSE 1  // tuning build: 0 launches K2 on its own
+#endif
+// Planner target: K1 segments per CU = K1's residency (three workgroups per CU), so the
+// whole launch is one round; a tuning build may override it at compile time.
+#ifndef VO_BA_SEGMENTS_PER_CU
+#define VO_BA_SEGMENTS_PER_CU 3
+#endif
+
+namespace vo {
+
+void* plan_host_alloc(size_t bytes, bool pinned) {
+  void* p = nullptr;
+  if (pinned) {
+    if (hipHostMalloc(&p, std::max<size_t>(bytes, 64), hipHostMallocDefault) != hipSuccess) throw std::bad_alloc();
+    return p;
+  }
+  return ::operator new(std::max<size_t>(bytes, 64), std::align_val_t(64));
+}
+
+void plan_host_free(void* p, bool pinned) noexcept {
+  if (!p) return;
+  if (pinned) (void)hipHostFree(p);
+  else ::operator delete(p, std::align_val_t(64));
+}
+
+namespace {
+
+template <class T, class A>
+void upload(DevBuf& buf, const std::vector<T, A>& v, hipStream_t st) {
+  buf.reserve(std::max<size_t>(v.size(), 1) * sizeof(T));
+  if (!v.empty())
+    VO_HIP_CHECK(hipMemcpyAsync(buf.ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
+}
+
+// A view into a device buffer owned by someone else (the packed tables, the misc block).
+struct DevView {
+  void* ptr = nullptr;
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(ptr);
+  }
+};
+// The plan's small tables packed into one device buffer: their places (256-byte aligned), their
+// host sources and the views that receive their device addresses.
+struct TablePack {
+  struct Part {
+    size_t off;
+    const void* src;
+    size_t n;
+    DevView* view;
+  };
+  std::vector<Part> parts;
+  size_t bytes = 0;
+  template <class V>
+  void add(const V& v, DevView& view) {
+    const size_t off = (bytes + 255) & ~(size_t)255, n = v.size() * sizeof(v[0]);
+    parts.push_back({off, v.data(), n, &view});
+    bytes = off + std::max<size_t>(n, 16);
+  }
+};
+
+std::atomic<uint64_t> g_ba_sessions{0};  // session ids, unique in the process
+
+}  // namespace
+
+class BAEngine {
+ public:
+  explicit BAEngine(vo_ctx* ctx) : ctx_(ctx) {}
+  ~BAEngine() {
+    if (h_state_ev_) {
+      (void)hipEventSynchronize(h_state_ev_);
+      (void)hipEventDestroy(h_state_ev_);
+    }
+  }
+
+  // Returns the new session id.  Every argument and plan check completes before any
+  // collective: with a communicator, all ranks then agree (min all-reduce of [ok, F, -F])
+  // and fail together, so one rank's bad shard is an error everywhere, not a hang.
+  uint64_t setup(const vo_ba_problem* prob) {
+    PLAN_T_START();
+    for (int64_t& v : setup_clock().ns) v = 0;
+    // the previous setup's chunk-image DMA may still read the page-locked images the
+    // planner is about to rewrite (a setup that failed after its upload returns unsynced)
+    VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+    PLAN_T(0, "setup: sync");
+    have_problem_ = false;
+    have_state_ = false;
+    std::string err = check_problem(prob);
+    // the last plan whose images reached the device: the next window's plan takes over its
+    // unchanged first-camera groups (ba_plan.h build_plan)
+    const bool prev_ok = plan_ok_;
+    plan_ok_ = false;
+    if (err.empty()) err = plan_window(*prob, prev_ok);  // sections 1 - 4
+    agree_on_plan(err);
+    VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_setup: %s", err.c_str());
+    PLAN_T(5, "setup: planned");
+    upload_images();
+    PLAN_T(6, "setup: images");
+    std::vector<int32_t> first = local_profile_first(plan_);
+    allreduce_min(first);
+    // banded K3 when the block bandwidth and F fit it (decided on first[], before the
+    // profile, whose step tables only the profile solver reads); the profile solver otherwise
+    const int F = plan_.n_free;
+    band_ = band_split(F, std::vector<int>(first.begin(), first.end()));
+    band_on_ = F > 0 && band_supported(F, band_.w, plan_.n_poses);
+    build_profile(plan_, first, !band_on_);
+    PLAN_T(7, "setup: profile");
+    prob_ = *prob;
+    prob_.point_ptr = nullptr;
+    prob_.obs_cam = nullptr;
+    prob_.obs_uv = nullptr;
+
+    const BAPlan& P = plan_;
+    // the plan's small tables, placed in one device buffer and sent with one copy (upload_tables)
+    TablePack pack;
+    pack.add(P.chunk_hdr, d_chunk_hdr_);
+    pack.add(P.slab_pos, d_slab_pos_);
+    pack.add(P.cam_pos, d_cam_pos_);
+    pack.add(P.seg_hdr, d_seg_hdr_);
+    d_solve_tab_.ptr = d_band_tab_.ptr = nullptr;  // whichever K3 runs adds its own
+    PLAN_T(8, "setup: uploads");
+    d_points_.reserve(std::max(1, P.n_points) * 24ull);
+    d_pose_[0].reserve(P.n_poses * 96ull);
+    d_pose_[1].reserve(P.n_poses * 96ull);
+    d_dc_.reserve(std::max(1, F) * 48ull);
+    d_slab_.reserve(std::max(1, P.n_slab_slots()) * 288ull);
+    d_slab_b_.reserve(std::max<size_t>(1, P.segcam_f.size()) * 48ull);
+    d_slab_cost_.reserve(std::max(1, P.n_segments()) * 8ull);
+    if (!band_on_) {
+      pack.add(P.solve_tab, d_solve_tab_);
+      const SolveTableLayout& TL = P.solve_layout;
+      const SolveLds in_lds = solve_lds_layout(true, P.n_prof_blocks(), F, TL.max_panel, TL.len, P.n_poses);
+      solve_lds_ = in_lds.total <= kSolveLdsMax;
+      solve_layout_ = solve_lds_ ? in_lds : solve_lds_layout(false, P.n_prof_blocks(), F, TL.max_panel, TL.len, P.n_poses);
+      VO_REQUIRE(solve_layout_.total <= kSolveLdsMax, VO_ERR_ARG,
+                 "vo_ba_setup: %d free poses / panel of %d blocks exceed the solver's LDS budget", F,
+                 TL.max_panel);
+      solve_lds_size_ = solve_layout_.total;
+    }
+    PLAN_T(9, "setup: bufs");
+    reduce_tables(pack);
+    upload_tables(pack);
+    PLAN_T(10, "setup: band");
+    if (!band_on_) profile_solve_set_attributes(solve_lds_size_);
+    PLAN_T(11, "setup: attrs");
+    std::copy(setup_clock().ns, setup_clock().ns + kSetupSections, setup_ns_);
+    // no sync: everything above is stream-ordered before the first iteration, pageable
+    // sources are staged when their copy is issued, and the page-locked chunk images are
+    // only rewritten after the sync at the top of the next setup
+    have_problem_ = true;
+    have_state_ = false;
+    pending_ = false;
+    cur_ = 0;
+    session_ = ++g_ba_sessions;
+    return session_;
+  }
+
+  // Pre-sizes what a window of about (n_poses, n_points, n_obs) needs, outside the keyframe
+  // calls: both plan objects' host arrays (plan_ and prev_plan_ alternate between setups; the
+  // page-locked chunk images included), every device buffer, the kernels' LDS attributes (the
+  // first one also loads the library's code object) and the state staging buffer.  It sets a
+  // synthetic window of that size up twice -- landmark p seen by a run of consecutive cameras,
+  // the runs spread over the window -- and then drops it: the context has no problem after it,
+  // and the next setup takes nothing over from it.  A later, larger window still grows what it
+  // needs (every array keeps a quarter of headroom).
+  void reserve(int n_poses, int n_points, int64_t n_obs, int n_fixed) {
+    VO_REQUIRE(n_poses >= 2 && n_points >= 1 && n_obs >= 2 * (int64_t)n_points && n_obs <= INT32_MAX &&
+                   n_fixed >= 0 && n_fixed < n_poses,
+               VO_ERR_ARG, "vo_ba_reserve: bad sizes");
+    VO_REQUIRE(!sharded(), VO_ERR_STATE,
+               "vo_ba_reserve: before vo_comm_init (a setup with a communicator is collective)");
+    const int len0 = (int)std::min<int64_t>(n_poses, n_obs / n_points);
+    const int64_t extra = std::min<int64_t>(n_obs - (int64_t)len0 * n_points, n_points);
+    std::vector<int32_t> ptr(n_points + 1), cam;
+    cam.reserve(n_obs);
+    for (int p = 0; p < n_points; ++p) {
+      const int len = std::min(n_poses, len0 + (p < extra ? 1 : 0));
+      const int c0 = (int)((int64_t)p * (n_poses - len + 1) / n_points);
+      for (int c = 0; c < len; ++c) cam.push_back(c0 + c);
+      ptr[p + 1] = (int32_t)cam.size();
+    }
+    std::vector<float> uv(2 * cam.size(), 0.0f);
+    vo_ba_problem pr{};
+    pr.n_poses = n_poses;
+    pr.n_points = n_points;
+    pr.n_obs = (int32_t)cam.size();
+    pr.n_fixed = n_fixed;
+    pr.fx = pr.fy = 500.0;
+    pr.lambda = 1.0;
+    pr.point_ptr = ptr.data();
+    pr.obs_cam = cam.data();
+    pr.obs_uv = uv.data();
+    for (int k = 0; k < 2; ++k) setup(&pr);
+    h_state_.reserve((3ull * n_points + 12ull * n_poses) * 8);
+    d_cost_.reserve(64 * 8);
+    VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+    plan_ok_ = false;  // nothing of the synthetic plan is taken over
+    have_problem_ = false;
+    have_state_ = false;
+  }
+
+  // The caller's session must be the engine's current problem (VO_ERR_STATE otherwise):
+  // a later vo_ba_setup on the same context replaces it, and its sizes with it.
+  void check_session(uint64_t s) const {
+    VO_REQUIRE(have_problem_ && s == session_, VO_ERR_STATE,
+               "BA session %llu is not this context's current problem (%llu): another vo_ba_setup replaced it",
+               (unsigned long long)s, (unsigned long long)session_);
+  }
+
+  void set_state(const double* poses, const double* points) {
+    VO_REQUIRE(have_problem_, VO_ERR_STATE, "vo_ba_set_state before vo_ba_setup");
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    // points gathered into internal order in the page-locked staging buffer, poses behind them
+    const size_t np = 3ull * P.n_points;
+    if (h_state_busy_) VO_HIP_CHECK(hipEventSynchronize(h_state_ev_));  // previous set_state's DMA
+    h_state_busy_ = false;
+    h_state_.reserve((np + 12ull * P.n_poses) * 8);
+    double* pts = h_state_.as<double>();
+    for (int q = 0; q < P.n_points; ++q)
+      for (int e = 0; e < 3; ++e) pts[3ull * q + e] = points[3ull * P.pt_perm[q] + e];
+    std::memcpy(pts + np, poses, P.n_poses * 96ull);
+    VO_HIP_CHECK(hipMemcpyAsync(d_pose_[0].ptr, pts + np, P.n_poses * 96ull, hipMemcpyHostToDevice, st));
+    if (P.n_points) VO_HIP_CHECK(hipMemcpyAsync(d_points_.ptr, pts, np * 8, hipMemcpyHostToDevice, st));
+    // not synchronised here: the next writer of the staging buffer waits for this event
+    if (!h_state_ev_) VO_HIP_CHECK(hipEventCreateWithFlags(&h_state_ev_, hipEventDisableTiming));
+    VO_HIP_CHECK(hipEventRecord(h_state_ev_, st));
+    h_state_busy_ = true;
+    VO_HIP_CHECK(hipMemsetAsync(d_status_.ptr, 0, sizeof(int), st));
+    if (fuse_ok_) VO_HIP_CHECK(hipMemsetAsync(d_colcnt_.ptr, 0, colcnt_bytes_, st));  // after a timed-out solve
+    cur_ = 0;
+    pending_ = false;
+    have_state_ = true;
+  }
+
+  void get_state(double* poses, double* points) {
+    require_state();
+    finalize();
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const size_t np = 3ull * P.n_points;
+    if (h_state_busy_) VO_HIP_CHECK(hipEventSynchronize(h_state_ev_));  // before reserve() may free it
+    h_state_busy_ = false;
+    h_state_.reserve((np + 12ull * P.n_poses) * 8);
+    double* pts = h_state_.as<double>();
+    VO_HIP_CHECK(hipMemcpyAsync(pts + np, d_pose_[cur_].ptr, P.n_poses * 96ull, hipMemcpyDeviceToHost, st));
+    if (P.n_points) VO_HIP_CHECK(hipMemcpyAsync(pts, d_points_.ptr, np * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    std::memcpy(poses, pts + np, P.n_poses * 96ull);
+    for (int q = 0; q < P.n_points; ++q)
+      for (int e = 0; e < 3; ++e) points[3ull * P.pt_perm[q] + e] = pts[3ull * q + e];
+  }
+
+  // iters GN iterations; sync=true finalises and reads the costs back.
+  int run(int iters, double* cost_out, bool sync) {
+    require_state();
+    VO_REQUIRE(iters >= 0, VO_ERR_ARG, "vo_ba_run: iters < 0");
+    hipStream_t st = ctx_->stream;
+    d_cost_.reserve((iters + 1) * 8ull);
+    for (int it = 0; it < iters; ++it) iteration(d_cost_.as<double>() + it, it + 1);
+    if (!sync) return VO_OK;
+    finalize_cost(d_cost_.as<double>() + iters);
+    std::vector<double> costs(iters + 1);
+    int status = 0;
+    VO_HIP_CHECK(hipMemcpyAsync(costs.data(), d_cost_.ptr, costs.size() * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    const bool timed_out = clear_failure(status);
+    if (status)  // iteration `status` (1-based) failed: the state is its linearisation point
+      for (int k = status; k <= iters; ++k) costs[k] = NAN;
+    if (cost_out) std::copy(costs.begin(), costs.end(), cost_out);
+    VO_REQUIRE(!timed_out, VO_ERR_HIP, "vo_ba_run: fused reduction timed out at iteration %d (a reducer workgroup never arrived)", status - 1);
+    if (status) {
+      set_error("vo_ba_run: reduced camera system not positive definite at iteration %d",
+                status - 1);
+      return VO_ERR_NOT_SPD;
+    }
+    return VO_OK;
+  }
+
+  // After a failed fused launch (any non-zero status; kBandStatusTimeout: the solver gave up
+  // waiting for its reducers) the reducer counter is re-zeroed -- the stream is synchronised,
+  // so every late reducer has counted itself by now -- and the timeout flag is stripped from
+  // the status word's iteration; a failed iteration's status word is re-zeroed on the device
+  // and the stream synchronised.  Returns whether a timeout was recorded.
+  bool clear_failure(int& status) {
+    hipStream_t st = ctx_->stream;
+    if (status && fuse_ok_) VO_HIP_CHECK(hipMemsetAsync(d_colcnt_.ptr, 0, colcnt_bytes_, st));
+    const bool timed_out = status & kBandStatusTimeout;
+    status &= ~kBandStatusTimeout;
+    if (status) {
+      VO_HIP_CHECK(hipMemsetAsync(d_status_.ptr, 0, sizeof(int), st));
+      VO_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return timed_out;
+  }
+
+  int gn_step(double* S_out, double* b_out, double* dc_out, double* cost_out) {
+    require_state();
+    hipStream_t st = ctx_->stream;
+    const BAPlan& P = plan_;
+    const int F = P.n_free;
+    d_cost_.reserve(8);
+    enqueue_lin(pending_ ? (kBacksub | kAccum) : kAccum);
+    enqueue_reduce();
+    std::vector<double> sys(sys_len_);
+    // the reduced system as K2 wrote it: before the solve (the profile solver factors it in
+    // place), or after the fused K2 + K3 launch (the banded K3 only reads it)
+    if (!fused()) VO_HIP_CHECK(hipMemcpyAsync(sys.data(), d_sys_.ptr, sys_len_ * 8, hipMemcpyDeviceToHost, st));
+    enqueue_solve(1);
+    if (fused()) VO_HIP_CHECK(hipMemcpyAsync(sys.data(), d_sys_.ptr, sys_len_ * 8, hipMemcpyDeviceToHost, st));
+    std::vector<double> dc(6ull * F);
+    int status = 0;
+    if (F) VO_HIP_CHECK(hipMemcpyAsync(dc.data(), d_dc_.ptr, dc.size() * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    cur_ ^= 1;
+    pending_ = true;
+    if (S_out) {  // K2's output layout (red_dst_) back to the dense symmetric S
+      const int n = 6 * F;
+      std::fill(S_out, S_out + (size_t)n * n, 0.0);
+      for (int i = 0; i < F; ++i)
+        for (int j = P.prof_first[i]; j <= i; ++j) {
+          const int d = red_dst_[P.prof_off[i] + j - P.prof_first[i]];
+          const double* blk = sys.data() + (d & ~kRedTranspose);
+          const bool tr = d & kRedTranspose;
+          for (int r = 0; r < 6; ++r)
+            for (int c = 0; c < 6; ++c) {
+              const double v = blk[tr ? 6 * c + r : 6 * r + c];
+              S_out[(size_t)(6 * i + r) * n + 6 * j + c] = v;
+              S_out[(size_t)(6 * j + c) * n + 6 * i + r] = v;
+            }
+        }
+    }
+    if (b_out)
+      for (int f = 0; f < F; ++f) std::copy(sys.begin() + red_rdst_[f], sys.begin() + red_rdst_[f] + 6, b_out + 6 * f);
+    if (dc_out) std::copy(dc.begin(), dc.end(), dc_out);
+    if (cost_out) *cost_out = sys[cost_off_];
+    const bool timed_out = clear_failure(status);
+    if (status) {
+      VO_REQUIRE(!timed_out, VO_ERR_HIP, "vo_ba_gn_step: fused reduction timed out (a reducer workgroup never arrived)");
+      set_error("vo_ba_gn_step: reduced camera system not positive definite");
+      return VO_ERR_NOT_SPD;
+    }
+    return VO_OK;
+  }
+
+  int stats(int64_t* out, int n) const {
+    const BAPlan& P = plan_;
+    int64_t v[12 + kSetupSections] = {P.n_chunks(), P.n_segments(), P.n_slab_slots(), (int64_t)P.slot_i.size(),
+                                      P.n_prof_blocks(), P.n_te, P.algorithmic_bytes_per_iter(), band_on_ ? 1 : 0,
+                                      P.reused_groups, P.reused_chunks, P.seg_obs};
+    for (int i = 0; i < kSetupSections; ++i) v[11 + i] = setup_ns_[i];  // the last setup's sections
+    // the banded K3's layout: 0 none (profile solver), 1 full, 2 ring, 3 split (two workgroups)
+    v[11 + kSetupSections] = !band_on_ ? 0 : band_lds_.split ? 3 : band_lds_.full ? 1 : 2;
+    const int k = std::min(n, 12 + kSetupSections);
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+  }
+
+ private:
+  void require_state() const {
+    VO_REQUIRE(have_problem_, VO_ERR_STATE, "BA: no problem set up");
+    VO_REQUIRE(have_state_, VO_ERR_STATE, "BA: no state set");
+  }
+
+  // ---- setup's steps, in its order ----------------------------------------------------------
+  static std::string check_problem(const vo_ba_problem* prob) {
+    if (!prob) return "null problem";
+    if (!(prob->n_poses >= 1 && prob->n_points >= 0 && prob->n_obs >= 0)) return "bad sizes";
+    if (!(prob->lambda >= 0.0)) return "lambda must be >= 0";
+    if (!((prob->n_points == 0 || prob->point_ptr) && (prob->n_obs == 0 || (prob->obs_cam && prob->obs_uv))))
+      return "null arrays";
+    if (prob->n_points == 0 && prob->n_obs != 0) return "observations without points";
+    return "";
+  }
+
+  // Plans the window into plan_ (the previous plan moves to prev_plan_, its device images to
+  // d_chunk_img_prev_).  Returns the planner's error message, empty on success.
+  std::string plan_window(const vo_ba_problem& pr, bool prev_ok) {
+    // K1 variant (a plan property, ba_plan.h plan_is_wave): the one-wave K1 at every size --
+    // cfg4's 13.7k chunks run in nine rounds of six per CU, faster than the four-wave K1's one
+    // round of two-chunk segments (148 against 222 us) -- with wave_chunks()
+    // chunks per segment; the four-wave K1 over multi-chunk segments only under the testing
+    // switch (vo_ba_testing_k1).  The packing target is a function of this window alone, so a
+    // plan that takes groups over from the previous one is the plan a scratch setup builds
+    // (take-over needs equal targets: build_plan checks).
+    const bool wave = ctx_->ba_k1_variant >= 0;
+    const int nw = wave ? wave_chunks(pr.n_obs) : 1;
+    std::vector<int32_t> zero_ptr(1, 0);
+    const int32_t* pp = pr.n_points ? pr.point_ptr : zero_ptr.data();
+    std::swap(plan_, prev_plan_);
+    d_chunk_img_.swap(d_chunk_img_prev_);
+    const BAPlan* prev = prev_ok ? &prev_plan_ : nullptr;
+    auto plan = [&](int seg_obs, int seg_chunks) {
+      return build_plan(plan_, pr.n_poses, pr.n_points, pr.n_obs, pr.n_fixed, pp, pr.obs_cam, pr.obs_uv, seg_obs, prev,
+                        seg_chunks);
+    };
+    const int seg_obs = seg_obs_grid(seg_obs_for(pr.n_obs, segments_target(ctx_->num_cus, wave)));
+    std::string err = plan(seg_obs, nw);
+    // six-chunk segments beyond one round (one workgroup per CU): plan with three
+    if (err.empty() && wave && ctx_->ba_k1_variant == 0 && nw == kWaveChunksOneRound &&
+        plan_.n_segments() > ctx_->num_cus)
+      err = plan(seg_obs, kWaveChunksRounds);
+    PLAN_T(4, "setup: returned");
+    // four-wave K1: every first-camera group ends in a partial segment, so the packing target
+    // may give more segments than one round holds; then pack once more, proportionally wider
+    // (on the grid; a function of the plan, which does not depend on prev)
+    const int round = segments_target(ctx_->num_cus, false);
+    for (int k = 0; k < 4 && err.empty() && !plan_is_wave(plan_.seg_obs) && plan_.n_segments() > round; ++k)
+      err = plan(seg_obs_grid((int64_t)plan_.seg_obs * plan_.n_segments() / round + 1), 1);
+    return err;
+  }
+
+  bool sharded() const { return ctx_->comm && ctx_->comm->nranks > 1; }
+
+  // Element-wise minimum of a small host vector over the ranks (nothing on one rank): upload,
+  // all-reduce on the stream, download, synchronise.
+  void allreduce_min(std::vector<int32_t>& v) {
+    if (!sharded() || v.empty()) return;
+    DevBuf tmp;
+    upload(tmp, v, ctx_->stream);
+    ctx_->comm->allreduce(tmp.as<int32_t>(), v.size(), true, ctx_->stream);
+    VO_HIP_CHECK(hipMemcpyAsync(v.data(), tmp.ptr, v.size() * 4, hipMemcpyDeviceToHost, ctx_->stream));
+    VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+  }
+
+  // The cross-rank agreement on [ok, F, -F]: a rank whose checks passed takes over the error
+  // of one whose did not.
+  void agree_on_plan(std::string& err) {
+    if (!sharded()) return;
+    const int32_t F = err.empty() ? plan_.n_free : 0;
+    std::vector<int32_t> agree = {err.empty() ? 1 : 0, F, -F};
+    allreduce_min(agree);
+    if (err.empty() && agree[0] == 0) err = "another rank's shard failed its checks";
+    if (err.empty() && agree[1] != -agree[2]) err = "ranks disagree on the number of free poses";
+  }
+
+  // The largest plan array first: from page-locked memory the copy runs while the host
+  // builds the profile and the K3 tables.  Images taken over from the previous plan are
+  // copied on the device, in runs of consecutive chunks.
+  void upload_images() {
+    const BAPlan& P = plan_;
+    const int nch = (int)P.chunk_img.size();
+    d_chunk_img_.reserve(std::max(nch, 1) * sizeof(ChunkImg));
+    ImgRuns R{};
+    int copied = 0;
+    auto flush = [&]() {
+      if (R.n == 0) return;
+      launch_img_copy(d_chunk_img_prev_.as<uint4>(), d_chunk_img_.as<uint4>(), R, copied, ctx_->stream);
+      VO_HIP_CHECK(hipGetLastError());
+      R.n = 0;
+      copied = 0;
+    };
+    for (int c0 = 0; c0 < nch;) {
+      const int src = c0 < (int)P.chunk_src.size() ? P.chunk_src[c0] : -1;
+      int c1 = c0 + 1;
+      while (c1 < nch && (src < 0 ? P.chunk_src[c1] < 0 : P.chunk_src[c1] == src + (c1 - c0))) ++c1;
+      if (src >= 0) {  // taken over: a run of the copy kernel
+        if (R.n == kImgRuns) flush();
+        R.src[R.n] = src;
+        R.dst[R.n] = c0;
+        copied += c1 - c0;
+        R.end[R.n++] = copied;
+      } else {  // built by this plan: from the page-locked images
+        VO_HIP_CHECK(hipMemcpyAsync(d_chunk_img_.as<ChunkImg>() + c0, P.chunk_img.data() + c0,
+                                    (size_t)(c1 - c0) * sizeof(ChunkImg), hipMemcpyHostToDevice, ctx_->stream));
+      }
+      c0 = c1;
+    }
+    flush();
+    plan_ok_ = true;
+  }
+
+  // K2's output layout -- the profile [S | b | cost], or the banded K3's columns (and that
+  // solver's layout and tables) --, its per-block table and the fused launch's readiness table.
+  void reduce_tables(TablePack& pack) {
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const int F = P.n_free, nprof = P.n_prof_blocks();
+    red_dst_.assign(std::max(1, nprof), 0);
+    red_rdst_.assign(std::max(1, F), 0);
+    size_t pad = 0;
+    if (band_on_) {
+      const int w = band_.w, CS = band_col_stride(w), top = band_.m + band_.s;
+      const int base_b = top * CS;
+      for (int i = 0; i < F; ++i) {
+        for (int j = P.prof_first[i]; j <= i; ++j) {
+          const int b = P.prof_off[i] + j - P.prof_first[i];
+          red_dst_[b] = i < top ? j * CS + 36 * (i - j) : (base_b + (F - 1 - i) * CS + 36 * (i - j)) | kRedTranspose;
+        }
+        red_rdst_[i] = i < top ? i * CS + 36 * (w + 1) : base_b + (F - 1 - i) * CS + 36 * (w + 1);
+      }
+      sys_len_ = (size_t)(F + band_.s) * CS + 1;
+      cost_off_ = (long)sys_len_ - 1;
+      pad = band_slot_stride(w);  // the ring loader's last LDS-DMA piece reads past the end
+      band_lds_ = band_lds_layout(F, band_, P.n_poses, !ctx_->ba_no_split);
+      band_tab_ = band_tables(F, band_, band_lds_);
+      pack.add(band_tab_.tab, d_band_tab_);
+      band_set_attributes(band_lds_);  // (a no-op unless the LDS size grows)
+      if (!band_lds_.full || band_lds_.split) d_fac_.reserve(band_fac_doubles(F, w) * 8);
+      if (band_lds_.split) {  // the split hand-offs' exchange area (front of fac); flags start clear
+        const SplitXch x = split_xch(band_tab_.n_merge, band_.s);
+        VO_REQUIRE((size_t)x.end() <= band_fac_doubles(F, w), VO_ERR_STATE, "band split: exchange area");
+        VO_HIP_CHECK(hipMemsetAsync(d_fac_.as<double>() + x.flag, 0, 3 * 16 * sizeof(double), st));
+      }
+    } else {
+      for (int b = 0; b < nprof; ++b) red_dst_[b] = 36 * b;
+      for (int f = 0; f < F; ++f) red_rdst_[f] = 36 * nprof + 6 * f;
+      sys_len_ = 36ull * nprof + 6ull * F + 1;
+      cost_off_ = (long)sys_len_ - 1;
+    }
+    d_sys_.reserve((sys_len_ + pad) * 8);
+    // entries K2 never writes (outside the profile, the bottom side's separator) stay 0
+    VO_HIP_CHECK(hipMemsetAsync(d_sys_.ptr, 0, (sys_len_ + pad) * 8, st));
+    // K2's per-block table: slab rows, the diagonal blocks' rhs entries, output offsets
+    red_meta_.assign(std::max(1, nprof), int4{0, 0, -1, -1});
+    red_out_.assign(std::max(1, nprof), int2{0, 0});
+    for (int i = 0; i < F; ++i)
+      for (int b = P.prof_off[i]; b < P.prof_off[i + 1]; ++b) {
+        const bool diag = P.prof_diag[b] != 0;
+        red_meta_[b] = int4{P.prof_src_ptr[b], P.prof_src_ptr[b + 1], diag ? P.camb_ptr[i] : -1,
+                            diag ? P.camb_ptr[i + 1] : -1};
+        red_out_[b] = int2{red_dst_[b], diag ? red_rdst_[i] : 0};
+      }
+    // the fused launch's readiness counters: the column each profile block's reducer stores
+    // into (top columns j of rows i < m + s, then bottom column F - 1 - i at m + s + F - 1 - i),
+    // the cost at F, and how many items each counter waits for
+    red_col_.assign(std::max(1, nprof), 0);
+    col_need_.assign(F + 1, 0);
+    if (band_on_) {
+      const int top = band_.m + band_.s;
+      for (int i = 0; i < F; ++i)
+        for (int b = P.prof_off[i]; b < P.prof_off[i + 1]; ++b) {
+          const int j = P.prof_first[i] + (b - P.prof_off[i]);
+          red_col_[b] = i < top ? j : top + (F - 1 - i);
+          ++col_need_[red_col_[b]];
+        }
+      col_need_[F] = 1;  // the cost item
+    }
+    pack.add(red_meta_, d_red_meta_);
+    pack.add(red_out_, d_red_out_);
+    pack.add(red_col_, d_red_col_);
+    pack.add(col_need_, d_col_need_);
+    // K2 fused into the banded K3's launch when every workgroup of it fits one round at
+    // one per CU (the solver's LDS): cfg3's 356 blocks make 178 reducers + the solver on
+    // MI355X's 256 CUs (fewer CUs, e.g. a partitioned device: K2 stays a launch of its own)
+    // (full mode only: the ring-mode solver reads sys with plain loads, so it must come from an
+    // earlier launch)
+    fuse_ok_ = VO_BA_FUSE && band_on_ && band_lds_.full && !band_lds_.split &&
+               band_fused_workgroups(nprof) + 1 <= ctx_->num_cus;
+  }
+
+  // One page-locked staging buffer, one device buffer, one copy (each table a pageable
+  // copy of its own cost several µs of host time apiece); both are rewritten only after the
+  // stream sync at the top of the next setup.  Then the tables' views, and the small zeroed
+  // buffers beside them.
+  void upload_tables(const TablePack& pack) {
+    hipStream_t st = ctx_->stream;
+    h_tab_.reserve(pack.bytes);
+    d_tab_.reserve(pack.bytes);
+    for (const TablePack::Part& q : pack.parts)
+      if (q.n) std::memcpy(h_tab_.as<char>() + q.off, q.src, q.n);
+    VO_HIP_CHECK(hipMemcpyAsync(d_tab_.ptr, h_tab_.ptr, pack.bytes, hipMemcpyHostToDevice, st));
+    for (const TablePack::Part& q : pack.parts) q.view->ptr = d_tab_.as<char>() + q.off;
+    // the status word, K2's fused-round counter and the zero block (masked prefetches)
+    d_misc_.reserve(kMiscBytes);
+    d_status_.ptr = d_misc_.ptr;
+    d_zero_.ptr = d_misc_.as<char>() + 256;
+    VO_HIP_CHECK(hipMemsetAsync(d_misc_.ptr, 0, kMiscBytes, st));
+    colcnt_bytes_ = band_col_count_bytes(plan_.n_free);
+    d_colcnt_.reserve(colcnt_bytes_);
+    VO_HIP_CHECK(hipMemsetAsync(d_colcnt_.ptr, 0, colcnt_bytes_, st));
+  }
+
+  // Planner target of one K1 round: as many segments as resident workgroups (three per CU,
+  // K1's __launch_bounds__ and LDS image).  A segment's time is about its chunk count times
+  // the per-chunk latency, so one round of longer segments beats two rounds of shorter ones
+  // (cfg4: 766 segments instead of 985; the cfg3 plan packs 678 either way).  Round 1's
+  // sweep (profiles/r01_segment_sweep.md) predates the three-per-CU K1.
+  // The one-wave K1 runs one chunk per segment: the largest target packs every
+  // segment as one chunk (seg_obs = 1).
+  static int segments_target(int num_cus, bool wave) {
+    return wave ? (1 << 30) : VO_BA_SEGMENTS_PER_CU * std::max(1, num_cus);
+  }
+  // Chunks per segment of the one-wave K1's plan (the testing switch's value if it sets one).
+  // Three instead of one: a third of the slab rows K2 reads for a barrier per segment; cfg3
+  // 14.89k -> 15.27k GN-iters/s (42 148 -> 15 538 rows), cfg4 3.91k -> 4.04k (K2 34 -> 16 us,
+  // K1 148 -> 158 us); two chunks sit between (profiles/r05_k1g).  Six (one 153 KB workgroup
+  // per CU, the same six waves per CU) halves the rows again, which pays while the segments fit
+  // one round: cfg3 15.71k -> 15.94k (246 segments, 8 175 rows; K1 24.7 -> 24.0 us, the fused
+  // K3 43.7 -> 43.3 us), but cfg4's nine rounds of single workgroups lose the overlap of one
+  // workgroup's combine with another's chunks: 4.09k -> 3.69k (profiles/r05_ab/k1_six_chunks).
+  // So six for windows whose six-chunk segments are predicted to fit one round (56 observations
+  // per chunk with padding, cfg3's; setup re-plans with three when they do not), else three.
+  // (48-observation chunks, tuning builds: eight waves per CU, two per SIMD)
+  static constexpr int kWaveChunksOneRound = std::min(kChunkObs >= 64 ? 6 : 8, kWaveMaxChunks),
+                       kWaveChunksRounds = std::min(3, kWaveMaxChunks);
+  int wave_chunks(int64_t n_obs) const {
+    if (ctx_->ba_k1_variant >= 1) return std::min(ctx_->ba_k1_variant, kWaveMaxChunks);
+    const int64_t one_round_obs = (int64_t)ctx_->num_cus * kWaveChunksOneRound * (kChunkObs * 7 / 8);
+    return n_obs * 10 <= one_round_obs * 11 ? kWaveChunksOneRound : kWaveChunksRounds;
+  }
+
+  LinArgs lin_args() {
+    const BAPlan& P = plan_;
+    LinArgs A;
+    A.n_fixed = P.n_fixed;
+    A.fx = prob_.fx; A.fy = prob_.fy; A.cx = prob_.cx; A.cy = prob_.cy;
+    A.lambda = prob_.lambda;
+    A.chunk_hdr = d_chunk_hdr_.as<int4>();
+    A.chunk_img = d_chunk_img_.as<ChunkImg>();
+    A.slab_pos = d_slab_pos_.as<int>();
+    A.cam_pos = d_cam_pos_.as<int>();
+    A.seg_hdr = d_seg_hdr_.as<int>();
+    A.points = d_points_.as<double>();
+    A.slab = d_slab_.as<double>();
+    A.slab_b = d_slab_b_.as<double>();
+    A.slab_cost = d_slab_cost_.as<double>();
+    A.pose_old = d_pose_[cur_ ^ 1].as<double>();
+    A.pose_new = d_pose_[cur_].as<double>();
+    A.dc = d_dc_.as<double>();
+    A.status = d_status_.as<int>();
+    A.stamps = nullptr;
+    return A;
+  }
+
+  void enqueue_lin(int mode) {
+    const int nseg = plan_.n_segments();
+    if (nseg <= 0) {
+      // no landmarks: empty slabs, zero cost
+      VO_HIP_CHECK(hipMemsetAsync(d_slab_cost_.ptr, 0, 8, ctx_->stream));
+      return;
+    }
+    LinArgs A = lin_args();
+    // one-wave K1 for plans of one chunk per segment (the chunk image of segment s is chunk s)
+    const bool wave = plan_is_wave(plan_.seg_obs);
+    const int nw = wave ? plan_.seg_chunks : 1;
+    VO_REQUIRE(!wave || ((int64_t)nseg * nw == plan_.n_chunks() && nw >= 1 && nw <= kWaveMaxChunks), VO_ERR_STATE,
+               "K1: segments of seg_chunks chunks expected");
+    A.nseg = nseg;
+    ctx_->prof.begin(ctx_->stream, kKBaLin);
+    if (stamps_on_) {  // one row per chunk (one-wave K1) or segment (four-wave K1)
+      d_stamps_.reserve((size_t)plan_.n_chunks() * kPhCount * 8);
+      A.stamps = d_stamps_.as<unsigned long long>();
+    }
+    launch_lin(A, mode, wave ? nw : 0, nseg, ctx_->stream);
+    ctx_->prof.end(ctx_->stream);
+    VO_HIP_CHECK(hipGetLastError());
+  }
+
+  // K2 runs inside the banded K3's launch (one rank: no all-reduce between them)
+  bool fused() const { return fuse_ok_ && !ctx_->ba_split_reduce && !sharded(); }
+
+  ReduceArgs reduce_args() const {
+    const BAPlan& P = plan_;
+    ReduceArgs R;
+    R.nprof = P.n_prof_blocks();
+    R.F = P.n_free;
+    R.nseg = std::max(P.n_segments(), plan_.n_segments() > 0 ? 0 : 1);
+    // damping on the camera diagonal: added once -- by rank 0 only when the partial
+    // systems of the landmark shards are all-reduced
+    R.lambda = (ctx_->comm && ctx_->comm->rank > 0) ? 0.0 : prob_.lambda;
+    R.meta = d_red_meta_.as<int4>();
+    R.out = d_red_out_.as<int2>();
+    R.slab = d_slab_.as<double>();
+    R.slab_b = d_slab_b_.as<double>();
+    R.slab_cost = d_slab_cost_.as<double>();
+    R.sys = d_sys_.as<double>();
+    R.cost_off = cost_off_;
+    R.status = d_status_.as<int>();
+    return R;
+  }
+
+  void enqueue_reduce() {
+    if (fused()) return;  // K3's reducer workgroups do it
+    const ReduceArgs R = reduce_args();
+    ctx_->prof.begin(ctx_->stream, kKBaReduce);
+    launch_reduce(R, R.nprof + 1, ctx_->stream);
+    ctx_->prof.end(ctx_->stream);
+    VO_HIP_CHECK(hipGetLastError());
+    if (sharded())
+      ctx_->comm->allreduce(d_sys_.as<double>(), sys_len_, false, ctx_->stream);
+  }
+
+  void launch_solve(const SolveArgs& A) {
+    if (band_on_) {
+      BandArgs B;
+      B.F = A.F;
+      B.w = band_.w;
+      B.m = band_.m;
+      B.nb = band_.nb;
+      B.s = band_.s;
+      B.nprof = A.nprof;
+      B.n_poses = A.n_poses;
+      B.n_fixed = A.n_fixed;
+      B.iter_tag = A.iter_tag;
+      B.cost_off = cost_off_;
+      B.merge = band_tab_.merge;
+      B.n_merge = band_tab_.n_merge;
+      B.tab = d_band_tab_.as<int>();
+      B.sys = A.sys;
+      B.zero = d_zero_.as<double>();
+      B.fac = band_lds_.full && !band_lds_.split ? nullptr : d_fac_.as<double>();
+      B.seq = ++band_seq_ == 0 ? ++band_seq_ : band_seq_;  // split hand-off flags: new every launch
+      B.cost_out = A.cost_out;
+      B.dc = A.dc;
+      B.pose_cur = A.pose_cur;
+      B.pose_next = A.pose_next;
+      B.status = A.status;
+      B.stamps = nullptr;
+      B.nred = fused() ? band_fused_workgroups(A.nprof) : 0;
+      B.red_drop = B.nred > 0 ? ctx_->ba_drop_reducers : 0;
+      B.red_count = d_colcnt_.as<unsigned>();
+      B.red_col = d_red_col_.as<int>();
+      B.col_need = d_col_need_.as<int>();
+      B.red = reduce_args();
+      if (stamps_on_) {  // per wave phase cycles, then realtime stamps of the solver and each reducer
+        d_stamps3_.reserve((8 * kBandStamps + 8 + 4 * (B.nred + 1)) * 8);
+        B.stamps = d_stamps3_.as<unsigned long long>();
+      }
+      launch_band_solve(B, band_lds_, ctx_->stream);
+      return;
+    }
+    launch_profile_solve(A, solve_lds_, solve_lds_size_, ctx_->stream);
+  }
+
+  void enqueue_solve(int iter_tag, double* cost_slot = nullptr) {
+    const BAPlan& P = plan_;
+    SolveArgs A;
+    A.F = P.n_free;
+    A.nprof = P.n_prof_blocks();
+    A.n_poses = P.n_poses;
+    A.n_fixed = P.n_fixed;
+    A.iter_tag = iter_tag;
+    A.max_panel = std::max(1, P.solve_layout.max_panel);
+    A.max_row_span = 0;
+    for (int k = 0; k < P.n_free; ++k) A.max_row_span = std::max(A.max_row_span, k - P.prof_first[k]);
+    A.lds_kf = (long)solve_layout_.kf;
+    A.lds_y = (long)solve_layout_.y;
+    A.lds_panel = (long)solve_layout_.panel;
+    A.lds_tab = (long)solve_layout_.tab;
+    A.lds_pose = (long)solve_layout_.pose;
+    A.tl = P.solve_layout;
+    A.tab = d_solve_tab_.as<int>();
+    A.cost_out = cost_slot;
+    A.sys = d_sys_.as<double>();
+    A.dc = d_dc_.as<double>();
+    A.pose_cur = d_pose_[cur_].as<double>();
+    A.pose_next = d_pose_[cur_ ^ 1].as<double>();
+    A.status = d_status_.as<int>();
+    A.stamps = nullptr;
+    if (stamps_on_) {
+      d_stamps3_.reserve(kS3Count * 8);
+      A.stamps = d_stamps3_.as<unsigned long long>();
+    }
+    ctx_->prof.begin(ctx_->stream, kKBaSolve);
+    launch_solve(A);
+    ctx_->prof.end(ctx_->stream);
+    VO_HIP_CHECK(hipGetLastError());
+  }
+
+  void iteration(double* d_cost_slot, int iter_tag) {
+    enqueue_lin(pending_ ? (kBacksub | kAccum) : kAccum);
+    enqueue_reduce();
+    enqueue_solve(iter_tag, d_cost_slot);  // K3 also stores the cost (no extra copy node)
+    cur_ ^= 1;
+    pending_ = true;
+  }
+
+  // Applies the pending point update (if any) and writes the cost at the
+  // resulting state into d_cost_slot.
+  void finalize_cost(double* d_cost_slot) {
+    enqueue_lin(pending_ ? kBacksub : 0);
+    pending_ = false;
+    // cost-only reduction (S/b untouched): reuse K2's last block
+    ReduceArgs R{};
+    R.nprof = 0;
+    R.F = 0;
+    R.nseg = std::max(1, plan_.n_segments());
+    R.slab_cost = d_slab_cost_.as<double>();
+    R.sys = d_cost_tmp();
+    R.cost_off = 0;
+    R.status = d_status_.as<int>();
+    launch_reduce(R, 1, ctx_->stream);
+    VO_HIP_CHECK(hipGetLastError());
+    if (sharded())
+      ctx_->comm->allreduce(R.sys, 1, false, ctx_->stream);
+    VO_HIP_CHECK(hipMemcpyAsync(d_cost_slot, R.sys, 8, hipMemcpyDeviceToDevice, ctx_->stream));
+  }
+
+  void finalize() {
+    if (!pending_) return;
+    d_cost_.reserve(8);
+    finalize_cost(d_cost_.as<double>());
+    VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+  }
+
+  double* d_cost_tmp() {
+    d_cost_tmp_.reserve(16);
+    return d_cost_tmp_.as<double>();
+  }
+
+  vo_ctx* ctx_;
+  BAPlan plan_{true};  // page-locked chunk images (async upload)
+  BAPlan prev_plan_{true};  // the previous window's plan (group take-over), or scratch
+  bool plan_ok_ = false;    // plan_ built and its images in d_chunk_img_
+  int64_t setup_ns_[kSetupSections] = {};  // the last setup's host sections (vo_ba_plan_stats)
+  vo_ba_problem prob_{};
+  bool have_problem_ = false, have_state_ = false, pending_ = false, solve_lds_ = false;
+  uint64_t session_ = 0;
+  int cur_ = 0;
+  size_t sys_len_ = 0, solve_lds_size_ = 0;
+  SolveLds solve_layout_{};
+  BandSplit band_{};
+  bool band_on_ = false;
+  bool fuse_ok_ = false;  // K2 fused into K3's launch (see fused())
+  unsigned band_seq_ = 0;  // split-mode K3 launches so far (their hand-off flag values)
+  BandLds band_lds_;
+  BandTables band_tab_;
+  // the plan's small tables (one upload per setup) and the views into them
+  HostBuf h_tab_;
+  DevBuf d_tab_;
+  DevView d_chunk_hdr_, d_seg_hdr_, d_slab_pos_, d_cam_pos_, d_solve_tab_, d_band_tab_, d_red_meta_, d_red_out_;
+  static constexpr size_t kMiscBytes = 256 + 512;
+  DevBuf d_misc_;  // [status | zero block (512 B)]
+  DevView d_status_, d_zero_;
+  DevBuf d_colcnt_;  // the fused launch's column readiness counters (band_col_count_bytes)
+  size_t colcnt_bytes_ = 0;
+  DevView d_red_col_, d_col_need_;
+  std::vector<int32_t> red_col_, col_need_;
+  std::vector<int4> red_meta_;
+  std::vector<int2> red_out_;
+  DevBuf d_fac_;
+  std::vector<int32_t> red_dst_, red_rdst_;  // K2 output offsets (host copies for gn_step)
+  long cost_off_ = 0;
+  HostBuf h_state_;  // page-locked staging of set_state / get_state
+  hipEvent_t h_state_ev_ = nullptr;  // set_state's upload from h_state_ done
+  bool h_state_busy_ = false;
+  DevBuf d_chunk_img_;  // K1's plan (the chunk images hold every list)
+  DevBuf d_chunk_img_prev_;  // the previous plan's images (prev_plan_)
+  DevBuf d_stamps_, d_stamps3_;
+  static constexpr bool stamps_on_ = kBaStamps;
+
+ public:
+  // Diagnostic: per-phase cycle sums of the last K1 launch (VO_BA_STAMPS=1 builds).
+  int read_stamps(uint64_t* out, int n) {
+    if (!stamps_on_) return 0;
+    // rows: chunks of a wave plan, segments of a four-wave plan
+    const int nseg = plan_is_wave(plan_.seg_obs) ? plan_.n_chunks() : plan_.n_segments();
+    std::vector<unsigned long long> h((size_t)nseg * kPhCount);
+    VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+    VO_HIP_CHECK(hipMemcpy(h.data(), d_stamps_.ptr, h.size() * 8, hipMemcpyDeviceToHost));
+    if (n < 0) {  // raw per-segment rows (kPhCount values each; the last two are absolute times)
+      const int k = std::min<int>(-n, (int)h.size());
+      std::copy(h.begin(), h.begin() + k, out);
+      return k;
+    }
+    int k = std::min(n, (int)kPhCount);
+    for (int i = 0; i < k; ++i) {
+      uint64_t acc = 0;
+      for (int g = 0; g < nseg; ++g) acc += h[(size_t)g * kPhCount + i];
+      out[i] = acc;
+    }
+    const int n3 = band_on_ ? 8 * kBandStamps : (int)kS3Count;  // K3: banded or profile solver
+    if (n >= kPhCount + n3 && d_stamps3_.ptr) {
+      // the banded solver's realtime stamps follow when the caller asked for them (fused launch)
+      const int nx = band_on_ && fused() ? 8 + 4 * (band_fused_workgroups(plan_.n_prof_blocks()) + 1) : 0;
+      const int n3x = n >= kPhCount + n3 + nx ? n3 + nx : n3;
+      VO_HIP_CHECK(hipMemcpy(out + kPhCount, d_stamps3_.ptr, n3x * 8, hipMemcpyDeviceToHost));
+      k += n3x;
+    }
+    return k;
+  }
+
+ private:
+  DevBuf d_points_, d_pose_[2], d_dc_, d_slab_, d_slab_b_, d_slab_cost_, d_sys_;
+  DevBuf d_cost_, d_cost_tmp_;
+};
+
+// ---- entry points used by api.hip -------------------------------------------------
+BAEngine* ba_engine(vo_ctx* ctx) {
+  if (!ctx->ba) ctx->ba.reset(new BAEngine(ctx));
+  return ctx->ba.get();
+}
+uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p) { return ba_engine(ctx)->setup(p); }
+void ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_fixed) {
+  ba_engine(ctx)->reserve(n_poses, n_points, n_obs, n_fixed);
+}
+void ba_check_session(vo_ctx* ctx, uint64_t s) { ba_engine(ctx)->check_session(s); }
+void ba_set_state(vo_ctx* ctx, const double* poses, const double* pts) {
+  ba_engine(ctx)->set_state(poses, pts);
+}
+void ba_get_state(vo_ctx* ctx, double* poses, double* pts) { ba_engine(ctx)->get_state(poses, pts); }
+int ba_run(vo_ctx* ctx, int iters, double* cost, bool sync) { return ba_engine(ctx)->run(iters, cost, sync); }
+int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost) {
+  return ba_engine(ctx)->gn_step(S, b, dc, cost);
+}
+int ba_stats(vo_ctx* ctx, int64_t* out, int n) { return ba_engine(ctx)->stats(out, n); }
+int ba_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_stamps(out, n); }
+
+}  // namespace vo
+
+vo_ctx::vo_ctx() = default;
+
+vo_ctx::~vo_ctx() {
+  ba.reset();
+  comm.reset();
+  if (stream) (void)hipStreamDestroy(stream);
+}

@@ -1,0 +1,100 @@
+// Arguments and host launches of the BA kernels in ba.hip (K1, K2, the profile K3, the chunk
+// image copy), called by the BA engine (ba_engine.hip).  The banded K3: ba_band.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+
+#include "ba_plan.h"
+#include "ba_reduce.h"
+
+namespace vo {
+
+// Diagnostic build only (make EXTRA=-DVO_BA_STAMPS=1): per-phase s_memtime stamps of K1
+// and the profile K3.  The product build executes none.
+#ifndef VO_BA_STAMPS
+#define VO_BA_STAMPS 0
+#endif
+constexpr bool kBaStamps = VO_BA_STAMPS != 0;
+constexpr int kPhCount = 16;  // values per K1 stamp row (ba.hip kPh*)
+constexpr int kS3Count = 10;  // values of the profile K3's stamp row (ba.hip kS3*)
+
+// K1 modes: back-substitute the pending step, linearise and accumulate the Schur blocks.
+enum { kBacksub = 1, kAccum = 2 };
+
+struct LinArgs {
+  int n_fixed;
+  double fx, fy, cx, cy, lambda;
+  const int4* chunk_hdr;  // kChunkHdr ints per chunk (BAPlan::chunk_hdr)
+  const ChunkImg* chunk_img;  // BAPlan::chunk_img
+  const int* slab_pos;        // BAPlan::slab_pos (window slot -> slab row)
+  const int* cam_pos;         // BAPlan::cam_pos (window camera -> rhs slab row)
+  const int* seg_hdr;     // kSegHdr ints per segment (BAPlan::seg_hdr)
+  double* points;
+  double* slab;
+  double* slab_b;
+  double* slab_cost;
+  const double* pose_old;  // linearisation of the pending step (back-substitution)
+  const double* pose_new;  // current linearisation point
+  const double* dc;        // pending pose update (6 per free camera)
+  const int* status;
+  unsigned long long* stamps;  // diagnostic build only: per segment phase cycles
+  int nseg;                    // segments
+};
+// One workgroup per segment (grid): the one-wave K1 of wave_chunks (1 .. kWaveMaxChunks) chunks
+// per segment, or the four-wave K1 (wave_chunks = 0).
+void launch_lin(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream_t st);
+
+// K2: nprof + 1 workgroups (the last sums the cost), or 1 with nprof = 0: the cost alone.
+void launch_reduce(const ReduceArgs& A, int workgroups, hipStream_t st);
+
+// K3: profile Cholesky solve S dc = b + pose update.
+struct SolveArgs {
+  int F, nprof, n_poses, n_fixed, iter_tag;
+  int max_panel, max_row_span;  // most panel blocks in a column; max k - first[k]
+  long lds_kf, lds_y, lds_panel, lds_pose, lds_tab;  // LDS offsets in doubles (solve_lds_layout)
+  SolveTableLayout tl;
+  const int* tab;      // BAPlan::solve_tab
+  double* cost_out;    // if set: receives the cost of this linearisation (sys tail)
+  double* sys;         // [S profile | b | cost]; factorised in place on the global path
+  double* dc;          // 6F out
+  const double* pose_cur;
+  double* pose_next;
+  int* status;
+  unsigned long long* stamps;  // diagnostic build only
+};
+
+struct SolveLds {
+  size_t prof, kf, y, panel, pose, tab, total;
+};
+constexpr size_t kSolveLdsMax = 160 * 1024 - 64;  // gfx950: 160 KiB per workgroup (+ s_fail)
+// LDS image: [profile 36*nprof (LDS path)] [per column: L 21 + pad 3 | r 6 | y'/x 6]
+// [y 6F] [4 private panels, 36 doubles per block] [step table ints]
+inline SolveLds solve_lds_layout(bool lds_profile, int nprof, int F, int max_panel, int tab_len,
+                                 int n_poses) {
+  SolveLds L;
+  L.prof = 0;
+  L.kf = lds_profile ? 36ull * nprof : 0;
+  L.y = L.kf + 36ull * F;
+  L.panel = L.y + 6ull * F;
+  L.pose = L.panel + 4ull * 36 * std::max(1, max_panel);
+  L.tab = L.pose + 12ull * n_poses;
+  L.total = L.tab * 8 + 4ull * std::max(1, tab_len);
+  return L;
+}
+// lds_profile: the profile is LDS resident (the layout it was sized with); lds_bytes its total.
+void launch_profile_solve(const SolveArgs& A, bool lds_profile, size_t lds_bytes, hipStream_t st);
+void profile_solve_set_attributes(size_t lds_bytes);  // (a no-op unless the LDS size grows)
+
+// Runs of consecutive chunk images copied from the previous plan's device images (ba.hip
+// ba_img_copy_kernel); they travel in the arguments.
+constexpr int kImgRuns = 48;
+struct ImgRuns {
+  int n;                    // runs in this launch
+  int src[kImgRuns], dst[kImgRuns], end[kImgRuns];  // run r: chunks [end[r-1], end[r]) of the launch
+};
+void launch_img_copy(const uint4* prev, uint4* cur, const ImgRuns& R, int chunks, hipStream_t st);
+
+}  // namespace vo

@@ -102,8 +102,8 @@ struct SiftWorkspace {
   }
 };
 
-class BAEngine;   // ba.hip
-struct Comm;      // ba.hip (RCCL communicator)
+class BAEngine;   // ba_engine.hip
+struct Comm;      // ba_comm.h (RCCL communicator or loopback group)
 
 // Kernel ids of the event profiler (vo_profile_* in include/vo_hip.h).
 enum KernelId {
