@@ -68,6 +68,21 @@ if k > 0:
     print("  first 5 starts", (t0[order[:5]] - base).tolist(), " last 5 starts", (t0[order[-5:]] - base).tolist())
     slow = np.argsort(dur)[-5:]
     print("  slowest segments", slow.tolist(), dur[slow].tolist())
+    nw = st_["chunks"] // max(st_["segments"], 1)
+    if st_["seg_obs"] == 1 and nw > 1 and len(r) == nw * st_["segments"]:
+        # workgroups of nw waves (rows = chunks, segment-major): the workgroup's duration, and what
+        # follows the point where its last wave has only the rhs rows, the cost butterfly, the
+        # barrier and the cross-chunk combine left (the row's start plus every phase but "write")
+        g0 = r[:, 8].reshape(-1, nw)
+        g1 = r[:, 9].reshape(-1, nw)
+        pre = (r[:, 8] + r[:, :8].sum(axis=1) - r[:, 6]).reshape(-1, nw)
+        wg = g1.max(axis=1) - g0.min(axis=1)
+        after = g1.max(axis=1) - pre.max(axis=1)
+        q = lambda v: f"{v.min()} {int(np.median(v))} {int(np.percentile(v, 90))} {v.max()}"
+        print(f"K1 workgroups of {nw} waves: duration min/median/p90/max: {q(wg)}")
+        print(f"  last wave's rhs start to the workgroup's end min/median/p90/max: {q(after)}")
+        print("  waves' own work done (rhs start) after the workgroup's start, median per wave:",
+              np.median(pre - g0.min(axis=1, keepdims=True), axis=0).astype(int).tolist())
     if len(sys.argv) > 2:  # per-segment rows for cost-model fitting: duration, phases, counts
         np.savetxt(sys.argv[2], np.column_stack([dur, r[:, :8], r[:, 10:16]]), fmt="%d",
                    header="dur " + " ".join(PHASES[:8]) + " " + " ".join(PHASES[10:16]))

@@ -673,7 +673,7 @@ struct alignas(16) LinWave {
   double X[kChunkPts][3];
   double L[kChunkPts][6];  // 1/l00, l10, 1/l11, l20, l21, 1/l22
   double h[kChunkPts][3];
-  double pose_n[kSegAllCams][12];  // after the linearisation: the chunk's b sums by window camera
+  alignas(16) double pose_n[kSegAllCams][12];  // after the linearisation: the chunk's b sums by window camera
   uint8_t valid[kChunkPts];
   // segments of several chunks (one wave each): per window slot the scratch row of this chunk's
   // block (0xFF: not active here), per window camera whether the chunk has its b, the cost
@@ -959,11 +959,20 @@ __device__ __forceinline__ void rhs_rows(LinWave& S, const LinArgs& A, int nac, 
 // run on their own LDS images without waiting on each other, leave their blocks in their scratch
 // rows, and after one workgroup barrier the segment's slots are summed over its chunks in chunk
 // order into one slab row each (fewer rows for K2: one per segment slot, not per chunk slot).
+// NW > 4: the waves of chunks 0..3 sum their own chunks' parts before that barrier, while the
+// two waves that share a SIMD still run, and add the late chunks' parts after it.
 static_assert(sizeof(LinWave::pose_n) >= kSegCams * 6 * sizeof(double), "the chunk's b sums fit pose_n");
 template <int MODE, bool kStamp, int NW>
 __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs A) {
   constexpr bool kGroup = NW > 1;
+  // the cross-chunk combine: its waves, whether they start before the late waves are done, and
+  // a thread's 16-byte pieces of the slots' blocks and of the rhs
+  constexpr int kCombWaves = NW < 4 ? NW : 4;
+  constexpr bool kEarly = NW > kCombWaves && (MODE & kAccum);
+  constexpr int kCombS = (kSegSlots * 18 + 64 * kCombWaves - 1) / (64 * kCombWaves);
+  constexpr int kCombB = (kSegCams * 3 + 64 * kCombWaves - 1) / (64 * kCombWaves);
   __shared__ LinWave Sw[NW];
+  __shared__ int s_arrive;
   static_assert(kLinLanesWave == 64, "one wave");
   const int wv = kGroup ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
   LinWave& S = Sw[wv];
@@ -989,6 +998,12 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
   for (int k = 0; k < 3; ++k) {
     i_acam[k] = SH16[16 + min((tid + 64 * k) / 12, kSegAllCams - 1)];
     i_wcam[k] = SH16[32 + min((tid + 64 * k) / 6, kSegCams - 1)];
+  }
+  if (kEarly) {  // the arrival word starts at zero for every wave (under the level-1 loads)
+    if (threadIdx.x == 0) s_arrive = 0;
+    lds_sync_wave();  // (a bare barrier: a fence would wait for the loads in flight)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
   }
   if (stat) return;  // a previous solve failed: state frozen
   const int nslots = g0.x, slot_off = g0.y, cam0 = g0.z, ncams = g0.w, na = g1.x;
@@ -1179,36 +1194,79 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
     if (tid == 0) A.slab_cost[seg] = cost;
   } else {
     if (tid == 0) S.wcost = cost;
-    __syncthreads();  // every wave's blocks, b sums, maps and cost
+    // The combine: segment slot s' block and window camera c's rhs, the chunks' parts summed in
+    // chunk order (only the chunks that have it), by 16-byte pieces: two neighbouring entries of
+    // one slab row, each with its own scalar sum.  The waves of the first kCombWaves chunks do
+    // it.  A segment of more chunks has two waves on some SIMDs, and those finish thousands of
+    // cycles after the others: the combining waves meet early at the arrival word and sum their
+    // pieces over their own chunks in registers while the late waves still run; after the
+    // barrier only the late chunks' parts and the stores are left.
     const int t = (int)threadIdx.x;
-    if (MODE & kAccum) {
-      // segment slot s, entry i: the chunks' blocks in chunk order (only the chunks that have it)
-      for (int e = t; e < nslots * 36; e += 64 * NW) {
-        const int s = e / 36, i = e - 36 * s;
-        double acc = 0.0;
-        bool any = false;
+    const int nps = nslots * 18, npb = ncams * 3;
+    double2 accS[kCombS], accB[kCombB];
+    bool anyS[kCombS], anyB[kCombB];
+    double2 *dstS[kCombS], *dstB[kCombB];
+    auto comb = [&](auto w0c, auto w1c) __attribute__((always_inline)) {
+      constexpr int W0 = decltype(w0c)::value, W1 = decltype(w1c)::value;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) {
+      for (int k = 0; k < kCombS; ++k) {
+        const int p = min(t + 64 * kCombWaves * k, max(nps - 1, 0));
+        const int s = p / 18, i = 2 * (p - 18 * s);
+        if constexpr (W0 == 0) {
+          accS[k] = make_double2(0.0, 0.0);
+          anyS[k] = false;
+          dstS[k] = reinterpret_cast<double2*>(A.slab + 36l * S.spos[s] + i);
+        }
+#pragma unroll
+        for (int w = W0; w < W1; ++w) {
           const int r = Sw[w].srow[s];
-          const double v = (&Sw[w].Jc[0][0])[36 * (r == 0xFF ? 0 : r) + i];
-          acc = r == 0xFF ? acc : any ? acc + v : v;
-          any = any || r != 0xFF;
+          const double2 v = *reinterpret_cast<const double2*>(&Sw[w].Jc[0][0] + 36 * (r == 0xFF ? 0 : r) + i);
+          accS[k].x = r == 0xFF ? accS[k].x : anyS[k] ? accS[k].x + v.x : v.x;
+          accS[k].y = r == 0xFF ? accS[k].y : anyS[k] ? accS[k].y + v.y : v.y;
+          anyS[k] = anyS[k] || r != 0xFF;
         }
-        A.slab[36l * S.spos[s] + i] = acc;
       }
-      for (int e = t; e < ncams * 6; e += 64 * NW) {
-        const int c = e / 6;
-        double acc = 0.0;
-        bool any = false;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) {
-          const bool on = Sw[w].crow[c] != 0;
-          const double v = (&Sw[w].pose_n[0][0])[e];
-          acc = !on ? acc : any ? acc + v : v;
-          any = any || on;
+      for (int k = 0; k < kCombB; ++k) {
+        const int p = min(t + 64 * kCombWaves * k, max(npb - 1, 0));
+        const int c = p / 3, i = 2 * (p - 3 * c);
+        if constexpr (W0 == 0) {
+          accB[k] = make_double2(0.0, 0.0);
+          anyB[k] = false;
+          dstB[k] = reinterpret_cast<double2*>(A.slab_b + 6l * S.cpos[c] + i);
         }
-        A.slab_b[6l * S.cpos[c] + (e - 6 * c)] = acc;
+#pragma unroll
+        for (int w = W0; w < W1; ++w) {
+          const bool on = Sw[w].crow[c] != 0;
+          const double2 v = *reinterpret_cast<const double2*>(&Sw[w].pose_n[0][0] + 6 * c + i);
+          accB[k].x = !on ? accB[k].x : anyB[k] ? accB[k].x + v.x : v.x;
+          accB[k].y = !on ? accB[k].y : anyB[k] ? accB[k].y + v.y : v.y;
+          anyB[k] = anyB[k] || on;
+        }
       }
+    };
+    using std::integral_constant;
+    if constexpr (kEarly) {
+      if (wv < kCombWaves) {
+        lds_sync_wave();  // this wave's blocks, b sums, maps and cost are in LDS
+        if (tid == 0) __hip_atomic_fetch_add(&s_arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        // waves of one resident workgroup, all of which arrive (the status test above is uniform)
+        while (__builtin_amdgcn_readfirstlane(
+                   __hip_atomic_load(&s_arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < kCombWaves)
+          __builtin_amdgcn_s_sleep(4);
+        asm volatile("" ::: "memory");
+        comb(integral_constant<int, 0>{}, integral_constant<int, kCombWaves>{});
+      }
+    }
+    __syncthreads();  // every wave's blocks, b sums, maps and cost
+    if ((MODE & kAccum) && wv < kCombWaves) {
+      comb(integral_constant<int, kEarly ? kCombWaves : 0>{}, integral_constant<int, NW>{});
+#pragma unroll
+      for (int k = 0; k < kCombS; ++k)
+        if (t + 64 * kCombWaves * k < nps) *dstS[k] = accS[k];
+#pragma unroll
+      for (int k = 0; k < kCombB; ++k)
+        if (t + 64 * kCombWaves * k < npb) *dstB[k] = accB[k];
     }
     if (t == 0) {
       double c = 0.0;

@@ -1015,8 +1015,10 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
   // fetched two steps ahead.  A chain step is the readlane broadcast of z_k from the
   // lanes holding it plus 6 FMAs; every x_k is formed in parallel at the end from z (LDS)
   // and the factor records.
-  // Full mode, the rest of the G blocks (rows the separator phase finalised: the top's
-  // separator rows and the bottom side's pseudo rows), then the back substitution.
+  // The rest of the G blocks, then the back substitution.  Split mode: the rows the separator
+  // phase finalised (the top's separator rows and the bottom side's pseudo rows); the full
+  // layout forms only the top's here (the separator's back substitution reads no other) and
+  // the pseudo rows on the waves idle under that back substitution, below.
   if (kFull && !failed) {
     if constexpr (kSplit) {  // the top: its separator rows
       if (!sbot) {  // (its rows before the separator: during phase A and after it)
@@ -1025,7 +1027,9 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
         for (int e = 6 * sp * w + tid; e < 12 * sp * w; e += NT) g_item(1, e);
       }
     } else {
-      const int nR = 6 * (sp > 0 ? 2 * sp * w : m * w);  // one-sided windows: every top row here
+      // two-sided windows: the top's separator rows only (the pseudo rows follow under the
+      // separator's back substitution, which does not read them); one-sided: every top row
+      const int nR = 6 * (sp > 0 ? sp : m) * w;
       for (int e = tid; e < nR; e += NT) g_item(sp > 0 ? 1 : 0, e);
     }
     __syncthreads();
@@ -1228,6 +1232,10 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
     if (role == kChain && side == 0 && sp > 0) {
       bs_init(m + sp - 1, INT_MAX);
       bs_go(m + sp - 1, m, INT_MAX);
+    } else if (kFull && !kSplit && sp > 0) {
+      // full layout: the seven waves idle under the separator's back substitution form the G
+      // blocks of the bottom side's pseudo rows (first read by the bottom's chain after it)
+      for (int e = 6 * sp * w + 64 * (wave - 1) + lane; e < 12 * sp * w; e += 64 * (kBandWaves - 1)) g_item(1, e);
     }
     BST(10);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the asm z stores retired
@@ -1266,18 +1274,19 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
   const double* const recB = kFull ? ringB : A.fac + (long)ncolT * CS;
   // (split mode: the late flag of a hand-off the bottom waited on after its failure verdict)
   const bool failed2 = failed || (kSplit && s_late != 0);
-  for (int c = tid; c < A.n_poses; c += NT) {
-    if (kSplit && (c >= A.n_fixed && c - A.n_fixed >= ncolT) != sbot) continue;  // the other side's poses
-    const double* T = pose_l + 12 * c;
-    double* out = A.pose_next + 12l * c;
-    if (failed2 || c < A.n_fixed) {
-      for (int e = 0; e < 12; ++e) out[e] = T[e];
-      if (c >= A.n_fixed)
-        for (int e = 0; e < 6; ++e) A.dc[6 * (c - A.n_fixed) + e] = 0.0;
-    } else {
+  // A free pose's lane (one dependent chain per pose) leaves x_k in z_k's place and the new
+  // pose in the staged pose's; fixed poses and a failed solve keep the staged pose.  Then every
+  // thread moves 16-byte pieces of the contiguous rows: pose_next in 96-byte rows, dc in 48-byte
+  // rows (zero after a failed solve), instead of the pose's lane storing 18 strided doubles.
+  // (split mode: each workgroup its own side's poses)
+  auto mine = [&](int G) __attribute__((always_inline)) { return !kSplit || (G >= 0 && G >= ncolT) == sbot; };
+  if (!failed2)
+    for (int c = A.n_fixed + tid; c < A.n_poses; c += NT) {
       const int G = c - A.n_fixed;
+      if (!mine(G)) continue;  // the other side's poses
+      double* T = pose_l + 12 * c;
       const double* rec = G < ncolT ? recT + (long)G * CS : recB + (long)(F - 1 - G) * CS;
-      double L[21], r[6], d[6];
+      double L[21], r[6], d[6], out[12];
 #pragma unroll
       for (int ii = 0; ii < 6; ++ii)
 #pragma unroll
@@ -1289,10 +1298,19 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
       ld6g(rec + 36 * R + 6, r);
       ld6g(zs + 6 * G, d);
       bwd6(L, r, d);
-      st6g(A.dc + 6 * G, d);
+      st6g(zs + 6 * G, d);
       se3_exp_apply(d, T, out);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) reinterpret_cast<double2*>(T)[e] = make_double2(out[2 * e], out[2 * e + 1]);
     }
-  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int e = tid; e < 6 * A.n_poses; e += NT)
+    if (mine(e / 6 - A.n_fixed))
+      reinterpret_cast<double2*>(A.pose_next)[e] = reinterpret_cast<const double2*>(pose_l)[e];
+  for (int e = tid; e < 3 * (A.n_poses - A.n_fixed); e += NT)
+    if (mine(e / 3))
+      reinterpret_cast<double2*>(A.dc)[e] = failed2 ? make_double2(0.0, 0.0) : reinterpret_cast<const double2*>(zs)[e];
   // A timeout is recorded whatever the earlier status (the counter then holds this launch's
   // reducers: the host re-zeroes it when it reads the flag); a failed factorisation only when
   // no earlier step failed (the status names the first failed iteration).

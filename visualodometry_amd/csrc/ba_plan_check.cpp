@@ -15,6 +15,9 @@
 // Input (binary): int32 n_poses, n_points, n_obs, n_fixed, seg_obs; point_ptr; obs_cam; obs_uv.
 // Optional argv[2]: seg_chunks (wave plans; default 1).
 // Prints "ok <chunks> <segments> <passes> <max chain (pair rows)>" or the first violation.
+// Optional argv[3] "combine" (seg_chunks > 1): a second line "combine <a> <b> <c> <d>", the
+// numbers of segments with fewer than four non-empty chunks, with a window slot held only by
+// chunks 4 and later, with one held only by chunks 0..3, and with every chunk non-empty.
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -60,6 +63,9 @@ int main(int argc, char** argv) {
   if (wave && P.seg_chunks != sc) FAIL("plan seg_chunks %d, asked %d", P.seg_chunks, sc);
   long passes = 0;
   int max_chain = 0;
+  // segments with fewer than four non-empty chunks, with a slot held only by chunks 4.., with a
+  // slot held only by chunks 0..3, and with every chunk non-empty (argv[3] "combine")
+  int comb_short = 0, comb_late = 0, comb_early = 0, comb_full = 0;
   for (int si = 0; si < P.n_segments(); ++si) {
     const int32_t* sh = &P.seg_hdr[(size_t)si * vo::kSegHdr];
     const int nslots = sh[0], so_ = sh[1], co = sh[2], ncams = sh[3];
@@ -153,6 +159,28 @@ int main(int argc, char** argv) {
         if (!upairs[wc].empty() && upairs[wc] != want) FAIL("chunk %d: camera %d track entries (U) differ", ch, wc);
       }
     }
+    if (wave && sc > 1) {
+      // the cross-chunk combine's cases: which chunks of the segment hold a slot's block (the
+      // first kCombFirst chunks' waves sum their own parts before the segment's barrier)
+      constexpr int kCombFirst = 4;
+      int live = 0;
+      std::vector<unsigned> in(nslots, 0u);
+      for (int ch = sh[5]; ch < sh[6]; ++ch) {
+        const int32_t* h = &P.chunk_hdr[(size_t)ch * vo::kChunkHdr];
+        live += h[1] > 0;
+        for (int s = 0; s < h[14]; ++s) in[P.chunk_img[ch].aslot[s]] |= 1u << (ch - sh[5]);
+      }
+      const unsigned first = (1u << kCombFirst) - 1;
+      bool late = false, early = false;
+      for (int s = 0; s < nslots; ++s) {
+        late = late || (in[s] != 0 && (in[s] & first) == 0);
+        early = early || (in[s] != 0 && (in[s] & ~first) == 0);
+      }
+      comb_short += live < kCombFirst;
+      comb_full += live == sc;
+      comb_late += late;
+      comb_early += early;
+    }
     if (wave) {
       for (int s = 0; s < nslots; ++s)
         if (!slot_seen[s]) FAIL("segment %d: window slot %d never written", si, s);
@@ -161,6 +189,8 @@ int main(int argc, char** argv) {
     }
   }
   std::printf("ok %d %d %ld %d\n", P.n_chunks(), P.n_segments(), passes, max_chain);
+  if (argc > 3 && std::string(argv[3]) == "combine")
+    std::printf("combine %d %d %d %d\n", comb_short, comb_late, comb_early, comb_full);
   std::fprintf(stderr, "slab_slots %d\n", P.n_slab_slots());
   return 0;
 }
