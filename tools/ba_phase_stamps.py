@@ -49,7 +49,8 @@ raw = np.zeros(nseg * NPH, dtype=np.uint64)
 k = ctx.lib.vo_ba_debug_stamps(ctx.handle, raw.ctypes.data_as(_lib.C.POINTER(_lib.C.c_uint64)), -raw.size)
 if k > 0:
     r = raw[:k].reshape(-1, NPH).astype(np.int64)
-    xcc = r[:, 15] >> 24  # the stamping lane's XCD (s_memtime counts per XCD)
+    xcc = (r[:, 15] >> 24) & 0xFF  # the stamping lane's XCD (s_memtime counts per XCD)
+    simd = (r[:, 15] >> 32) & 3  # and its wave's SIMD
     r[:, 15] &= 0xFFFFFF
     t0, t1 = r[:, 8], r[:, 9]
     dur = t1 - t0
@@ -83,6 +84,15 @@ if k > 0:
         print(f"  last wave's rhs start to the workgroup's end min/median/p90/max: {q(after)}")
         print("  waves' own work done (rhs start) after the workgroup's start, median per wave:",
               np.median(pre - g0.min(axis=1, keepdims=True), axis=0).astype(int).tolist())
+        # which waves share a SIMD: the placements seen, and how often waves (0, 4) and (1, 5) pair up
+        sw = simd.reshape(-1, nw)
+        pats, cnt = np.unique(sw, axis=0, return_counts=True)
+        top = np.argsort(-cnt)[:4]
+        print("  SIMD of each wave, most frequent placements:",
+              [(pats[i].tolist(), int(cnt[i])) for i in top], f"of {len(sw)} workgroups")
+        if nw > 4:
+            pair = np.all(sw[:, 4:] == sw[:, :nw - 4], axis=1)
+            print(f"  waves 4.. on the SIMD of waves 0..: {int(pair.sum())} of {len(sw)} workgroups")
     if len(sys.argv) > 2:  # per-segment rows for cost-model fitting: duration, phases, counts
         np.savetxt(sys.argv[2], np.column_stack([dur, r[:, :8], r[:, 10:16]]), fmt="%d",
                    header="dur " + " ".join(PHASES[:8]) + " " + " ".join(PHASES[10:16]))

@@ -352,7 +352,7 @@ template <bool kStamp>
 struct Stamper {
   // the stamping lane (thread 0, or lane 0 of each one-wave segment) and its output row;
   // s_memtime counts per XCD (clocks of different XCDs are unrelated), so the row's
-  // window-camera count carries the XCD id in bits 24..31
+  // window-camera count carries the XCD id in bits 24..31 (and the wave's SIMD id in bits 32..33)
   unsigned long long t = 0, acc[kPhCount] = {};
   bool lead = false;
   int row = 0;
@@ -363,7 +363,9 @@ struct Stamper {
       acc[kPhT0] = t = __builtin_amdgcn_s_memtime();
       unsigned xcc;
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-      acc[kPhCams] = (unsigned long long)xcc << 24;
+      // HW_ID (hwreg 4) bits 4..5: the SIMD this wave runs on, kept in bits 32..33
+      const unsigned simd = __builtin_amdgcn_s_getreg(4 | (4 << 6) | ((2 - 1) << 11));
+      acc[kPhCams] = (unsigned long long)xcc << 24 | (unsigned long long)simd << 32;
     }
   }
   __device__ __forceinline__ void start() { start(threadIdx.x == 0, blockIdx.x); }
@@ -962,6 +964,17 @@ __device__ __forceinline__ void rhs_rows(LinWave& S, const LinArgs& A, int nac, 
 // NW > 4: the waves of chunks 0..3 sum their own chunks' parts before that barrier, while the
 // two waves that share a SIMD still run, and add the late chunks' parts after it.
 static_assert(sizeof(LinWave::pose_n) >= kSegCams * 6 * sizeof(double), "the chunk's b sums fit pose_n");
+
+// A 16-byte piece of a slab row from the combine, stored write-through (sc1): its readers are
+// K2's workgroups on other XCDs, and a line left dirty in this XCD's L2 is written back at the
+// kernel's end, on the next launch's path.  No flag or fence goes with it (the kernel boundary
+// orders it as before).  The s_nop covers the wait state a wide store's data registers need.
+__device__ __forceinline__ void slab_store(double2* p, double2 v) {
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  const f64x2 d = {v.x, v.y};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" ::"v"(p), "v"(d) : "memory");
+}
+
 template <int MODE, bool kStamp, int NW>
 __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs A) {
   constexpr bool kGroup = NW > 1;
@@ -975,6 +988,19 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
   __shared__ int s_arrive;
   static_assert(kLinLanesWave == 64, "one wave");
   const int wv = kGroup ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0;
+  // NW > 4: waves 4.. run on the SIMDs of waves 0.. (measured: in every workgroup), and the
+  // arbiter gives the older wave of a pair nearly every issue slot, so the younger one finishes
+  // ~9k cycles after it, the last of them alone on its SIMD.  The younger wave holds priority 1
+  // from its first instruction until its elimination is done (about half of a chunk's own work),
+  // the older one has the rest: the pair ends closer together and the workgroup earlier.  wv is
+  // an SGPR, so both s_setprio sit under scalar branches.
+  constexpr bool kPrio = kEarly;
+  if constexpr (kPrio)
+    if (wv >= kCombWaves) __builtin_amdgcn_s_setprio(1);
+  auto prio_drop = [&]() __attribute__((always_inline)) {
+    if constexpr (kPrio)
+      if (wv >= kCombWaves) __builtin_amdgcn_s_setprio(0);
+  };
   LinWave& S = Sw[wv];
   const int seg = blockIdx.x, tid = (int)threadIdx.x & 63, chk = seg * NW + wv;
   Stamper<kStamp> st;
@@ -1170,6 +1196,7 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
     }
     lds_sync_wave();
     st.mark(kPhElim);
+    prio_drop();
 
     // Schur items: lane j sums active slot j's whole block (copies of a heavy slot balance
     // the lanes, each its own slab row); then the rhs by camera-row lanes
@@ -1263,10 +1290,10 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
       comb(integral_constant<int, kEarly ? kCombWaves : 0>{}, integral_constant<int, NW>{});
 #pragma unroll
       for (int k = 0; k < kCombS; ++k)
-        if (t + 64 * kCombWaves * k < nps) *dstS[k] = accS[k];
+        if (t + 64 * kCombWaves * k < nps) slab_store(dstS[k], accS[k]);
 #pragma unroll
       for (int k = 0; k < kCombB; ++k)
-        if (t + 64 * kCombWaves * k < npb) *dstB[k] = accB[k];
+        if (t + 64 * kCombWaves * k < npb) slab_store(dstB[k], accB[k]);
     }
     if (t == 0) {
       double c = 0.0;
