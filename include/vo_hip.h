@@ -198,7 +198,7 @@ int vo_ba_set_state(vo_ctx* ctx, uint64_t session, const double* poses, const do
 int vo_ba_get_state(vo_ctx* ctx, uint64_t session, double* poses, double* points);
 /* Runs `iters` pure Gauss-Newton iterations (every step accepted) on the
  * device-resident state.  cost_out (iters+1 doubles, may be NULL): sum of
- * squared residuals before each iteration and after the last one.
+ * squared residuals (of rho under vo_ba_set_robust) before each iteration and after the last one.
  * Returns VO_ERR_NOT_SPD (state left at the last good iterate) if the reduced
  * camera system is not positive definite. */
 int vo_ba_run(vo_ctx* ctx, uint64_t session, int iters, double* cost_out);
@@ -211,6 +211,20 @@ int vo_ba_run_async(vo_ctx* ctx, uint64_t session, int iters);
  * cost_out: 1 double.  The state is advanced by the step. */
 int vo_ba_gn_step(vo_ctx* ctx, uint64_t session, double* S_out, double* b_out, double* dc_out,
                   double* cost_out);
+/* Robust cost: huber_delta = delta >= 0 in pixels, 0 (the default of every vo_ba_setup) is the
+ * plain sum of squares.  For an observation with raw residual r, n^2 = r.r: n^2 <= delta^2 gives
+ * rho = n^2; otherwise rho = 2 delta n - delta^2, and the linearisation scales r and both
+ * Jacobians by s = sqrt(delta / n) (first-order IRLS).  Every cost the API reports is then
+ * sum(rho).  Valid any time after vo_ba_setup; the new delta holds from the next linearisation
+ * (a pending step's landmark update is applied first, under the delta it was computed with).
+ * VO_ERR_ARG for a negative or non-finite delta.  With a communicator every rank sets it on its
+ * own shard. */
+int vo_ba_set_robust(vo_ctx* ctx, uint64_t session, double huber_delta);
+/* Per observation, in the order of vo_ba_problem.obs_cam (n_obs doubles each, either pointer
+ * may be NULL): the raw, unweighted squared reprojection error in pixels^2 and the camera-frame
+ * depth z, at the device-resident state (after any pending landmark update).  With a
+ * communicator: the rank's own observations. */
+int vo_ba_residuals(vo_ctx* ctx, uint64_t session, double* err2_out, double* depth_out);
 /* One-call convenience: setup + set_state + run + get_state. */
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points,
                 int iters, double* cost_out);

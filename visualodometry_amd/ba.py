@@ -12,6 +12,14 @@ hook ``VisualOdometry._create_keyframe`` (``src/modules/vo.py:252-288``):
 Model (identical to ``oracle/ba_ref.py``): residual ``pi(K (R_cw X + t_cw)) - uv``
 with the no-distortion pinhole of ``frontend.py:139``, cost ``sum ||r||^2``,
 left se(3) pose increments, the first ``n_fixed`` poses fixed, pure GN.
+
+Robust cost (off by default): ``huber=delta`` in pixels replaces ``||r||^2`` by the Huber
+``rho`` (``||r||^2`` up to ``delta``, ``2 delta ||r|| - delta^2`` beyond) and scales each
+observation's residual and Jacobians by ``sqrt(delta / ||r||)`` in the linearisation
+(first-order IRLS; ``tests/ba_robust_ref.py`` restates it on the oracle); every reported cost is
+then ``sum rho``.  ``residuals()`` / ``optimize(..., return_residuals=True)`` give the raw squared
+reprojection error and depth per observation, so a caller can drop the tracks the solve ended
+up disagreeing with.
 """
 
 from __future__ import annotations
@@ -47,6 +55,10 @@ class BAResult:
     cost_per_iter: np.ndarray = field(default_factory=lambda: np.zeros(0))
     status: str = "ok"  # "ok" | "not_spd" | "skipped"
     message: str = ""
+    # optimize(return_residuals=True): raw squared reprojection error (px^2) and camera-frame
+    # depth per observation at the returned state, in the window's own observation order
+    obs_err2: np.ndarray | None = None
+    obs_depth: np.ndarray | None = None
 
 
 def poses_to_rt(poses_cw: np.ndarray) -> np.ndarray:
@@ -90,11 +102,12 @@ def csr_from_obs_pt(n_points: int, obs_pt: np.ndarray):
     return order, ptr_
 
 
-def group_window(n_points: int, window: "BAWindow"):
+def group_window(n_points: int, window: "BAWindow", return_order: bool = False):
     """The window's observations grouped by landmark -> (point_ptr, obs_cam, obs_uv).
     Windows built landmark by landmark (dropin/hooks.py ``KeyframeWindow.build``) are
     already grouped: their arrays pass through unchanged; others are reordered by
-    ``csr_from_obs_pt``."""
+    ``csr_from_obs_pt``.  ``return_order``: also the reordering (grouped position -> window
+    observation), ``None`` when the arrays passed through."""
     obs_pt = _as_index32(window.obs_pt)
     obs_cam = np.asarray(window.obs_cam)
     obs_uv = np.asarray(window.obs_uv, dtype=np.float32).reshape(-1, 2)
@@ -103,10 +116,12 @@ def group_window(n_points: int, window: "BAWindow"):
     rc = _lib.load().vo_ba_group_by_point(int(n_points), obs_pt.size, ptr(obs_pt, C.c_int32), None,
                                           ptr(point_ptr, C.c_int32))
     if rc == _lib.VO_OK:
-        return point_ptr, obs_cam, obs_uv
+        return (point_ptr, obs_cam, obs_uv, None) if return_order else (point_ptr, obs_cam, obs_uv)
     if rc != 1:
         raise ValueError("obs_pt out of range")
     order, point_ptr = csr_from_obs_pt(n_points, obs_pt)
+    if return_order:
+        return point_ptr, obs_cam[order], obs_uv[order], order
     return point_ptr, obs_cam[order], obs_uv[order]
 
 
@@ -186,7 +201,7 @@ class BASession:
     """
 
     def __init__(self, K, point_ptr, obs_cam, obs_uv, n_poses: int, n_fixed: int = 2,
-                 lam: float = 0.0, ctx: _lib.Context | None = None):
+                 lam: float = 0.0, ctx: _lib.Context | None = None, huber: float = 0.0):
         self.ctx = ctx or _lib.context()
         self.point_ptr = np.ascontiguousarray(point_ptr, dtype=np.int32)
         self.obs_cam = np.ascontiguousarray(obs_cam, dtype=np.int32)
@@ -202,6 +217,21 @@ class BASession:
         # the problem's id on this context: a later setup on the same context (another
         # session) makes every call below fail with VO_ERR_STATE instead of misreading
         self.session = int(sid.value)
+        if huber:  # a new problem starts with the plain cost
+            self.set_robust(huber)
+
+    def set_robust(self, delta: float) -> None:
+        """Huber ``delta`` in pixels for the later linearisations; 0 is the plain cost."""
+        check(self.ctx.lib.vo_ba_set_robust(self.ctx.handle, self.session, float(delta)), "vo_ba_set_robust")
+
+    def residuals(self):
+        """``(err2, depth)`` per observation in the order of ``obs_cam``: the raw (unweighted)
+        squared reprojection error and the camera-frame depth at the device state."""
+        err2 = np.empty(self.obs_cam.size)
+        depth = np.empty(self.obs_cam.size)
+        check(self.ctx.lib.vo_ba_residuals(self.ctx.handle, self.session, ptr(err2, C.c_double),
+                                           ptr(depth, C.c_double)), "vo_ba_residuals")
+        return err2, depth
 
     def set_state(self, poses_cw: np.ndarray, points: np.ndarray) -> None:
         rt = np.ascontiguousarray(poses_to_rt(poses_cw))
@@ -267,16 +297,22 @@ class BASession:
 class SlidingWindowBA:
     """``SlidingWindowBA(K, cfg).optimize(window) -> BAResult``.
 
-    ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda``; any
+    ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda`` / ``ba_huber``; any
     missing knob takes the keyword default.  Degenerate windows come back with
     ``status != "ok"`` instead of raising, so ``process_frame`` keeps the
     reference's print-and-continue failure style (``vo.py:240-245``).
     """
 
-    def __init__(self, K, cfg=None, *, iters: int = 10, lam: float = 0.0, device: int | None = None):
+    def __init__(self, K, cfg=None, *, iters: int = 10, lam: float = 0.0, huber: float = 0.0,
+                 device: int | None = None):
         self.K = np.asarray(K, dtype=np.float64)
         self.iters = int(getattr(cfg, "ba_iters", iters))
         self.lam = float(getattr(cfg, "ba_lambda", lam))
+        self.huber = float(getattr(cfg, "ba_huber", huber))  # Huber delta in pixels, 0: off
+        # a configuration error must not turn into "every window skipped" (optimize() maps the
+        # library's VO_ERR_ARG to a skipped window)
+        if not (np.isfinite(self.huber) and self.huber >= 0.0):
+            raise ValueError(f"ba_huber must be finite and >= 0, got {self.huber}")
         self.device = device
 
     def reserve(self, n_poses: int, n_points: int, obs_per_point: float = 5.0, n_fixed: int = 2) -> None:
@@ -287,23 +323,31 @@ class SlidingWindowBA:
         n_obs = max(2 * n_points, int(round(obs_per_point * n_points)))
         _lib.ba_reserve(_lib.context(self.device), max(2, int(n_poses)), n_points, n_obs, int(n_fixed))
 
-    def optimize(self, window: BAWindow) -> BAResult:
+    def optimize(self, window: BAWindow, return_residuals: bool = False) -> BAResult:
         poses = np.asarray(window.poses_cw, dtype=np.float64)
         pts = np.asarray(window.points, dtype=np.float64).reshape(-1, 3)
         n_fixed = min(int(window.n_fixed), poses.shape[0])
         if poses.shape[0] == 0 or pts.shape[0] == 0 or np.asarray(window.obs_cam).size == 0 \
                 or poses.shape[0] <= n_fixed:
             return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", "empty window")
-        point_ptr, obs_cam, obs_uv = group_window(pts.shape[0], window)
+        point_ptr, obs_cam, obs_uv, order = group_window(pts.shape[0], window, return_order=True)
         ctx = _lib.context(self.device)
+        err2 = depth = None
         try:
-            sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx)
+            sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
+                             huber=self.huber)
             sess.set_state(poses, pts)
             rc, costs = sess.run(self.iters)
             P, X = sess.get_state()
+            if return_residuals:
+                err2, depth = sess.residuals()
+                if order is not None:  # back from the grouped order to the window's own
+                    e, d = np.empty_like(err2), np.empty_like(depth)
+                    e[order], d[order] = err2, depth
+                    err2, depth = e, d
         except VoError as e:
             if e.code == _lib.VO_ERR_ARG:
                 return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", str(e))
             raise
         status = "ok" if rc == _lib.VO_OK else "not_spd"
-        return BAResult(P, X, costs, status)
+        return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth)

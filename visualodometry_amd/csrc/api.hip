@@ -744,6 +744,22 @@ int vo_ba_gn_step(vo_ctx* ctx, uint64_t session, double* S_out, double* b_out, d
   return g != VO_OK ? g : rc;
 }
 
+int vo_ba_set_robust(vo_ctx* ctx, uint64_t session, double huber_delta) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_set_robust(ctx, huber_delta);
+  });
+}
+
+int vo_ba_residuals(vo_ctx* ctx, uint64_t session, double* err2_out, double* depth_out) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_residuals(ctx, err2_out, depth_out);
+  });
+}
+
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points, int iters,
                 double* cost_out) {
   uint64_t s = 0;

@@ -28,6 +28,10 @@
 //       folded in, back substitution, and the left se(3) pose update T <- exp(dc^) T.
 // The point update dp = L^-T(-h - sum Z^T dc) is applied by the next K1 (or a
 // back-substitute-only K1), which recomputes the same linearisation bit for bit.
+// Under a Huber cost (LinArgs::huber > 0, DESIGN.md §Robust cost) K1's kRobust instantiations
+// scale each observation's residual and Jacobians by huber_scale (ba_math.h) where they are
+// formed; the plain instantiations are untouched.  ba_obs_residual_kernel reads out the raw
+// squared residual and the depth of every observation (vo_ba_residuals).
 // ba_img_copy_kernel copies chunk images taken over from the previous window's plan.
 #include "ba_kernels.h"
 
@@ -68,7 +72,10 @@ struct alignas(16) LinShared {
 // three K1 workgroups per CU (the cfg3 plan then runs in a single round)
 static_assert(sizeof(LinShared) <= 160 * 1024 / 3, "K1 LDS image");
 
-// R1: residual and Jacobians, one lane per observation.
+// R1: residual and Jacobians, one lane per observation.  kRob (DESIGN.md §Robust cost): the
+// Huber scale s of the raw residual multiplies r and both Jacobians (through the four projection
+// derivatives every Jacobian entry is linear in), and the cost sums rho.
+template <bool kRob>
 __device__ __forceinline__ void lin_obs(LinShared& S, const LinArgs& A, const double (*pose)[12],
                                         int nob, double& cost) {
   for (int o = threadIdx.x; o < nob; o += kLinThreads) {
@@ -80,13 +87,20 @@ __device__ __forceinline__ void lin_obs(LinShared& S, const LinArgs& A, const do
     const double z = T[6] * X0 + T[7] * X1 + T[8] * X2 + T[11];
     const double iz = rcp_nr(z);
     const float2 m = reinterpret_cast<const float2*>(S.img.uv)[o];
-    const double r0 = A.fx * x * iz + A.cx - (double)m.x;
-    const double r1 = A.fy * y * iz + A.cy - (double)m.y;
-    cost += r0 * r0 + r1 * r1;
+    double r0 = A.fx * x * iz + A.cx - (double)m.x;
+    double r1 = A.fy * y * iz + A.cy - (double)m.y;
+    if constexpr (!kRob) cost += r0 * r0 + r1 * r1;
+    double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
+    double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+    if constexpr (kRob) {
+      double rho;
+      const double s = huber_scale(r0, r1, A.huber, A.huber2, rho);
+      cost += rho;
+      r0 *= s; r1 *= s;
+      j00 *= s; j02 *= s; j11 *= s; j12 *= s;
+    }
     S.r[o][0] = r0;
     S.r[o][1] = r1;
-    const double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
-    const double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
     double* jc = S.Jc[o];
     jc[0] = j00;
     jc[1] = 0.0;
@@ -230,7 +244,7 @@ __device__ __forceinline__ void lin_eliminate(LinShared& S, int nte) {
 __device__ __forceinline__ void chunk_linearize(LinShared& S, const LinArgs& A,
                                                 const double (*pose)[12], int nob,
                                                 int nte, int npt, double& cost) {
-  lin_obs(S, A, pose, nob, cost);
+  lin_obs<false>(S, A, pose, nob, cost);
   __syncthreads();
   lin_reduce(S, A, nte, npt);
   __syncthreads();
@@ -243,6 +257,9 @@ __device__ __forceinline__ void chunk_linearize(LinShared& S, const LinArgs& A,
 // back-substitution -V^-1 (g + sum_t W_t^T dc) without forming W or Z.  V, the pivot
 // test and the Cholesky are point_block's, so a landmark frozen in the pending step's
 // camera system (invalid V) is not moved; fixed cameras contribute dc = 0.
+// kRob: the scale s comes from the raw residual at that point, before Jc dc is added (lin_obs's
+// huber_scale on the same values: the pending step's own weights), and multiplies r + Jc dc and Jp.
+template <bool kRob>
 __device__ __forceinline__ void chunk_backsub(LinShared& S, const LinArgs& A, int nob, int npt,
                                               int p0) {
   for (int o = threadIdx.x; o < nob; o += kLinThreads) {
@@ -257,8 +274,14 @@ __device__ __forceinline__ void chunk_backsub(LinShared& S, const LinArgs& A, in
     const float2 m = reinterpret_cast<const float2*>(S.img.uv)[o];
     double r0 = A.fx * x * iz + A.cx - (double)m.x;
     double r1 = A.fy * y * iz + A.cy - (double)m.y;
-    const double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
-    const double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+    double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
+    double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+    if constexpr (kRob) {
+      double rho;
+      const double s = huber_scale(r0, r1, A.huber, A.huber2, rho);
+      r0 *= s; r1 *= s;
+      j00 *= s; j02 *= s; j11 *= s; j12 *= s;
+    }
     const int lc = S.img.te_lcam[te];
     if (lc >= 0) {  // + Jc dc (rows of lin_obs's Jc)
       const double* d = S.dcw[lc];
@@ -391,6 +414,7 @@ __global__ __launch_bounds__(kLinThreads, 3) void ba_lin_kernel(LinArgs A) {  //
   __shared__ LinShared S;
   Stamper<kStamp> st;
   st.start();
+  constexpr bool kRob = (MODE & kRobust) != 0;
   const int seg = blockIdx.x, tid = threadIdx.x;
   // one load level: the status word, the segment header (uniform) and this thread's
   // camera ids (fixed offsets in the header); then poses and the pending update
@@ -471,17 +495,17 @@ __global__ __launch_bounds__(kLinThreads, 3) void ba_lin_kernel(LinArgs A) {  //
     st.mark(kPhLoad);
 
     if (MODE & kBacksub) {
-      chunk_backsub(S, A, nob, npt, p0);
+      chunk_backsub<kRob>(S, A, nob, npt, p0);
       __syncthreads();
       st.mark(kPhBacksub);
     }
 
     if (!(MODE & kAccum)) {
-      lin_obs(S, A, S.pose_n, nob, cost);  // cost at the updated state
+      lin_obs<kRob>(S, A, S.pose_n, nob, cost);  // cost at the updated state
       rotate();
       continue;
     }
-    lin_obs(S, A, S.pose_n, nob, cost);
+    lin_obs<kRob>(S, A, S.pose_n, nob, cost);
     __syncthreads();
     st.mark(kPhLinObs);
     lin_reduce(S, A, nte, npt);
@@ -727,8 +751,9 @@ __device__ __forceinline__ bool point_block_w(const LinWave& S, double lambda, i
 
 // Residual and Jacobians of observation o at pose T (lin_obs / chunk_backsub arithmetic);
 // r and Jp into the Zb region, Jc (kJc) into S.Jc.  The back substitution (kBack) adds
-// Jc dc for a free camera (dc non-null) and sums no cost.
-template <bool kJc, bool kBack>
+// Jc dc for a free camera (dc non-null) and sums no cost.  kRob: as lin_obs / chunk_backsub -- the
+// Huber scale of the raw residual (before Jc dc) on r and the Jacobians, the cost sums rho.
+template <bool kJc, bool kBack, bool kRob>
 __device__ __forceinline__ void obs_lin_w(LinWave& S, const LinArgs& A, const double* T, int o,
                                           const double* dc, double& cost) {
   const int q = S.img.obs_pt[o];
@@ -740,13 +765,20 @@ __device__ __forceinline__ void obs_lin_w(LinWave& S, const LinArgs& A, const do
   const float2 m = reinterpret_cast<const float2*>(S.img.uv)[o];
   double r0 = A.fx * x * iz + A.cx - (double)m.x;
   double r1 = A.fy * y * iz + A.cy - (double)m.y;
-  const double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
-  const double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+  double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
+  double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+  if constexpr (kRob) {
+    double rho;
+    const double s = huber_scale(r0, r1, A.huber, A.huber2, rho);
+    if (!kBack) cost += rho;
+    r0 *= s; r1 *= s;
+    j00 *= s; j02 *= s; j11 *= s; j12 *= s;
+  }
   if (kBack && dc) {
     r0 += j00 * dc[0] + j02 * dc[2] + (j02 * y) * dc[3] + (j00 * z - j02 * x) * dc[4] - (j00 * y) * dc[5];
     r1 += j11 * dc[1] + j12 * dc[2] + (j12 * y - j11 * z) * dc[3] - (j12 * x) * dc[4] + (j11 * x) * dc[5];
   }
-  if (!kBack) cost += r0 * r0 + r1 * r1;
+  if (!kBack && !kRob) cost += r0 * r0 + r1 * r1;
   S.zb[kZbR + 2 * o] = r0;
   S.zb[kZbR + 2 * o + 1] = r1;
   if (kJc) {  // compressed rows (jc_load): row 0 without column 1, row 1 without column 0
@@ -978,6 +1010,7 @@ __device__ __forceinline__ void slab_store(double2* p, double2 v) {
 template <int MODE, bool kStamp, int NW>
 __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs A) {
   constexpr bool kGroup = NW > 1;
+  constexpr bool kRob = (MODE & kRobust) != 0;
   // the cross-chunk combine: its waves, whether they start before the late waves are done, and
   // a thread's 16-byte pieces of the slots' blocks and of the rhs
   constexpr int kCombWaves = NW < 4 ? NW : 4;
@@ -1096,7 +1129,7 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
     // dp = -V^-1 sum Jp^T (r + Jc dc) per landmark (chunk_backsub)
     if (tid < nob) {
       const int lc = S.img.obs_lcam[tid];
-      obs_lin_w<false, true>(S, A, &pose_o[12 * S.img.acam[tid]], tid, lc >= 0 ? &dcw[6 * lc] : nullptr, cost);
+      obs_lin_w<false, true, kRob>(S, A, &pose_o[12 * S.img.acam[tid]], tid, lc >= 0 ? &dcw[6 * lc] : nullptr, cost);
     }
     lds_sync_wave();
     if (tid < npt) {
@@ -1118,7 +1151,7 @@ __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs
   }
 
   // residuals and Jacobians at the current linearisation point (cost at the updated state)
-  if (tid < nob) obs_lin_w<(MODE & kAccum) != 0, false>(S, A, S.pose_n[S.img.acam[tid]], tid, nullptr, cost);
+  if (tid < nob) obs_lin_w<(MODE & kAccum) != 0, false, kRob>(S, A, S.pose_n[S.img.acam[tid]], tid, nullptr, cost);
   if (MODE & kAccum) {
     lds_sync_wave();
     st.mark(kPhLinObs);
@@ -1761,6 +1794,32 @@ __global__ __launch_bounds__(64) void ba_img_copy_kernel(const uint4* __restrict
 }
 static_assert(sizeof(ChunkImg) / 16 <= 192, "three 16-byte pieces per lane");
 
+// The read-out of vo_ba_residuals: one lane per observation in the problem's order; K1's
+// projection arithmetic (lin_obs: the same operation order, rcp_nr), unweighted.  A template, so
+// that it is emitted where it is instantiated (launch_obs_residual, the end of this unit), behind
+// every K1 instantiation, so the plain K1 kernels keep the place in the code object they had
+// before this kernel existed.  An observation, not a law: emitted ahead of them, two benchmark
+// jobs of three runs read 0.0-0.1 % lower, which is about the run-to-run spread (DESIGN.md
+// §Robust cost); a later kernel placed ahead of K1 changes the layout again and should be
+// measured the same way.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void ba_obs_residual_kernel(ObsResidualArgs A) {
+  const int o = blockIdx.x * kThreads + threadIdx.x;
+  if (o >= A.n_obs) return;
+  const double* T = A.poses + 12l * A.obs_cam[o];
+  const double* X = A.points + 3l * A.obs_pt[o];
+  const double X0 = X[0], X1 = X[1], X2 = X[2];
+  const double x = T[0] * X0 + T[1] * X1 + T[2] * X2 + T[9];
+  const double y = T[3] * X0 + T[4] * X1 + T[5] * X2 + T[10];
+  const double z = T[6] * X0 + T[7] * X1 + T[8] * X2 + T[11];
+  const double iz = rcp_nr(z);
+  const float2 m = A.obs_uv[o];
+  const double r0 = A.fx * x * iz + A.cx - (double)m.x;
+  const double r1 = A.fy * y * iz + A.cy - (double)m.y;
+  A.err2[o] = r0 * r0 + r1 * r1;
+  A.depth[o] = z;
+}
+
 // ---- host launches (ba_kernels.h) ---------------------------------------------------------
 // K1 of one mode: the one-wave kernel of nw = 1 .. kWaveMaxChunks chunks per segment, else
 // (nw = 0) the four-wave kernel.
@@ -1797,7 +1856,14 @@ void launch_lin(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream
     case kAccum: lin_launch<kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
     case kBacksub | kAccum: lin_launch<kBacksub | kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
     case kBacksub: lin_launch<kBacksub>(A, wave_chunks, dim3(grid), st, nws); break;
-    default: lin_launch<0>(A, wave_chunks, dim3(grid), st, nws); break;
+    case 0: lin_launch<0>(A, wave_chunks, dim3(grid), st, nws); break;
+    // the Huber variants (A.huber > 0): instantiations of their own, the ones above keep their code
+    case kRobust | kAccum: lin_launch<kRobust | kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
+    case kRobust | kBacksub | kAccum:
+      lin_launch<kRobust | kBacksub | kAccum>(A, wave_chunks, dim3(grid), st, nws);
+      break;
+    case kRobust | kBacksub: lin_launch<kRobust | kBacksub>(A, wave_chunks, dim3(grid), st, nws); break;
+    default: lin_launch<kRobust>(A, wave_chunks, dim3(grid), st, nws); break;
   }
 }
 
@@ -1817,6 +1883,14 @@ void profile_solve_set_attributes(size_t lds_bytes) {
 
 void launch_img_copy(const uint4* prev, uint4* cur, const ImgRuns& R, int chunks, hipStream_t st) {
   hipLaunchKernelGGL(ba_img_copy_kernel, dim3(chunks), dim3(64), 0, st, prev, cur, R);
+}
+
+// (last: the read-out kernel is instantiated here, see ba_obs_residual_kernel)
+void launch_obs_residual(const ObsResidualArgs& A, hipStream_t st) {
+  constexpr int kThreads = 256;
+  if (A.n_obs <= 0) return;
+  hipLaunchKernelGGL(ba_obs_residual_kernel<kThreads>, dim3((A.n_obs + kThreads - 1) / kThreads), dim3(kThreads), 0,
+                     st, A);
 }
 
 }  // namespace vo

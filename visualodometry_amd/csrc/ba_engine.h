@@ -17,6 +17,8 @@ void ba_set_state(vo_ctx* ctx, const double* poses, const double* pts);
 void ba_get_state(vo_ctx* ctx, double* poses, double* pts);
 int ba_run(vo_ctx* ctx, int iters, double* cost, bool sync);
 int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost);
+void ba_set_robust(vo_ctx* ctx, double huber_delta);
+void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
 int ba_stats(vo_ctx* ctx, int64_t* out, int n);
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n);
 

@@ -171,6 +171,8 @@ class BAEngine {
     have_state_ = false;
     pending_ = false;
     cur_ = 0;
+    huber_ = 0.0;  // every problem starts with the plain cost
+    obs_uploaded_ = false;
     session_ = ++g_ba_sessions;
     return session_;
   }
@@ -269,6 +271,63 @@ class BAEngine {
     std::memcpy(poses, pts + np, P.n_poses * 96ull);
     for (int q = 0; q < P.n_points; ++q)
       for (int e = 0; e < 3; ++e) points[3ull * P.pt_perm[q] + e] = pts[3ull * q + e];
+  }
+
+  // The Huber delta of the later linearisations (0: the plain cost and its kernels).  A pending
+  // step was solved under the old delta: its landmark back substitution is enqueued first.
+  void set_robust(double delta) {
+    VO_REQUIRE(have_problem_, VO_ERR_STATE, "vo_ba_set_robust before vo_ba_setup");
+    VO_REQUIRE(std::isfinite(delta) && delta >= 0.0, VO_ERR_ARG, "vo_ba_set_robust: huber_delta must be finite and >= 0");
+    if (delta == huber_) return;
+    apply_pending();
+    huber_ = delta;
+  }
+
+  // Raw squared reprojection error and camera-frame depth of every observation, in the order of
+  // the problem's obs_cam, at the device state (a pending back substitution applied first).  The
+  // problem-order observation arrays go to the device on a session's first call: rebuilt from the
+  // plan's internal-order copies (the caller's arrays are not kept), so setup uploads nothing
+  // for them.
+  void residuals(double* err2_out, double* depth_out) {
+    require_state();
+    apply_pending();
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const size_t M = (size_t)P.n_obs;
+    if (M == 0) return;
+    if (!obs_uploaded_) {
+      std::vector<int32_t> cam(M), pt(M);
+      std::vector<float> uv(2 * M);
+      VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "vo_ba_residuals: the plan has no observation order");
+      for (size_t pos = 0; pos < M; ++pos) {  // internal position -> problem observation (ba_plan.h)
+        const size_t o = (size_t)P.obs_order[pos];
+        cam[o] = P.obs_cam[pos];
+        pt[o] = P.te_pt[P.obs_te[pos]];
+        uv[2 * o] = P.obs_uv[2 * pos];
+        uv[2 * o + 1] = P.obs_uv[2 * pos + 1];
+      }
+      upload(d_obs_cam_, cam, st);
+      upload(d_obs_pt_, pt, st);
+      upload(d_obs_uv_, uv, st);
+      VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
+      obs_uploaded_ = true;
+    }
+    d_obs_out_.reserve(2 * M * 8);
+    ObsResidualArgs A;
+    A.n_obs = (int)M;
+    A.fx = prob_.fx; A.fy = prob_.fy; A.cx = prob_.cx; A.cy = prob_.cy;
+    A.obs_cam = d_obs_cam_.as<int>();
+    A.obs_pt = d_obs_pt_.as<int>();
+    A.obs_uv = d_obs_uv_.as<float2>();
+    A.poses = d_pose_[cur_].as<double>();
+    A.points = d_points_.as<double>();
+    A.err2 = d_obs_out_.as<double>();
+    A.depth = d_obs_out_.as<double>() + M;
+    launch_obs_residual(A, st);
+    VO_HIP_CHECK(hipGetLastError());
+    if (err2_out) VO_HIP_CHECK(hipMemcpyAsync(err2_out, A.err2, M * 8, hipMemcpyDeviceToHost, st));
+    if (depth_out) VO_HIP_CHECK(hipMemcpyAsync(depth_out, A.depth, M * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
   }
 
   // iters GN iterations; sync=true finalises and reads the costs back.
@@ -642,9 +701,20 @@ class BAEngine {
     A.dc = d_dc_.as<double>();
     A.status = d_status_.as<int>();
     A.stamps = nullptr;
+    A.huber = huber_;
+    A.huber2 = huber_ * huber_;
     return A;
   }
 
+  // The pending step's landmark update alone (a back-substitute-only K1 under the delta the step
+  // was solved with): no reduction, no collective, no synchronisation.
+  void apply_pending() {
+    if (!pending_) return;
+    enqueue_lin(kBacksub);
+    pending_ = false;
+  }
+
+  // mode: kBacksub | kAccum; the Huber instantiations are chosen here (huber_ > 0).
   void enqueue_lin(int mode) {
     const int nseg = plan_.n_segments();
     if (nseg <= 0) {
@@ -664,7 +734,7 @@ class BAEngine {
       d_stamps_.reserve((size_t)plan_.n_chunks() * kPhCount * 8);
       A.stamps = d_stamps_.as<unsigned long long>();
     }
-    launch_lin(A, mode, wave ? nw : 0, nseg, ctx_->stream);
+    launch_lin(A, huber_ > 0.0 ? mode | kRobust : mode, wave ? nw : 0, nseg, ctx_->stream);
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
   }
@@ -896,6 +966,11 @@ class BAEngine {
  private:
   DevBuf d_points_, d_pose_[2], d_dc_, d_slab_, d_slab_b_, d_slab_cost_, d_sys_;
   DevBuf d_cost_, d_cost_tmp_;
+  double huber_ = 0.0;  // Huber delta in pixels, 0: plain cost (set_robust)
+  // residuals(): the problem-order observation arrays (uploaded on a session's first call) and
+  // its output [err2 | depth]
+  bool obs_uploaded_ = false;
+  DevBuf d_obs_cam_, d_obs_pt_, d_obs_uv_, d_obs_out_;
 };
 
 // ---- entry points used by api.hip -------------------------------------------------
@@ -916,6 +991,8 @@ int ba_run(vo_ctx* ctx, int iters, double* cost, bool sync) { return ba_engine(c
 int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost) {
   return ba_engine(ctx)->gn_step(S, b, dc, cost);
 }
+void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta); }
+void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }
 int ba_stats(vo_ctx* ctx, int64_t* out, int n) { return ba_engine(ctx)->stats(out, n); }
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_stamps(out, n); }
 

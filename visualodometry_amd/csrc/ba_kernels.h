@@ -21,8 +21,9 @@ constexpr bool kBaStamps = VO_BA_STAMPS != 0;
 constexpr int kPhCount = 16;  // values per K1 stamp row (ba.hip kPh*)
 constexpr int kS3Count = 10;  // values of the profile K3's stamp row (ba.hip kS3*)
 
-// K1 modes: back-substitute the pending step, linearise and accumulate the Schur blocks.
-enum { kBacksub = 1, kAccum = 2 };
+// K1 modes: back-substitute the pending step, linearise and accumulate the Schur blocks; kRobust
+// selects the Huber instantiations (LinArgs::huber > 0), the other four are the plain-cost kernels.
+enum { kBacksub = 1, kAccum = 2, kRobust = 4 };
 
 struct LinArgs {
   int n_fixed;
@@ -42,6 +43,7 @@ struct LinArgs {
   const int* status;
   unsigned long long* stamps;  // diagnostic build only: per segment phase cycles
   int nseg;                    // segments
+  double huber, huber2;        // Huber delta (pixels) and delta^2; read by the kRobust modes only
 };
 // One workgroup per segment (grid): the one-wave K1 of wave_chunks (1 .. kWaveMaxChunks) chunks
 // per segment, or the four-wave K1 (wave_chunks = 0).
@@ -87,6 +89,21 @@ inline SolveLds solve_lds_layout(bool lds_profile, int nprof, int F, int max_pan
 // lds_profile: the profile is LDS resident (the layout it was sized with); lds_bytes its total.
 void launch_profile_solve(const SolveArgs& A, bool lds_profile, size_t lds_bytes, hipStream_t st);
 void profile_solve_set_attributes(size_t lds_bytes);  // (a no-op unless the LDS size grows)
+
+// Per-observation read-out (ba_obs_residual_kernel): the raw squared reprojection error and the
+// camera-frame depth of every observation at the given state, in the problem's observation order.
+struct ObsResidualArgs {
+  int n_obs;
+  double fx, fy, cx, cy;
+  const int* obs_cam;     // problem order: camera
+  const int* obs_pt;      // problem order: landmark in the plan's internal order
+  const float2* obs_uv;   // problem order: measurement
+  const double* poses;    // 12 per camera
+  const double* points;   // 3 per landmark, internal order
+  double* err2;           // n_obs out
+  double* depth;          // n_obs out
+};
+void launch_obs_residual(const ObsResidualArgs& A, hipStream_t st);
 
 // Runs of consecutive chunk images copied from the previous plan's device images (ba.hip
 // ba_img_copy_kernel); they travel in the arguments.

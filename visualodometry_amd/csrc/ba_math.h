@@ -143,6 +143,26 @@ __device__ __forceinline__ double rcp_nr(double z) {
   return __builtin_isinf(r0) ? r0 : r;
 }
 
+// Huber cost of one observation (DESIGN.md §Robust cost): raw residual (r0, r1), n2 = r.r;
+// n2 <= delta^2: rho = n2, scale 1; else n = sqrt(n2), rho = 2 delta n - delta^2 and the scale
+// s = sqrt(delta / n) of the residual and its Jacobians (first-order IRLS).  1/n and sqrt(delta/n)
+// by v_rsq_f64 with two Newton steps each (~1 ulp; no IEEE sqrt or division sequence), selects
+// instead of branches.  K1's linearisation and its back substitution both call this on the same
+// values, so the pending step is recomputed under the weights it was solved with.
+__device__ __forceinline__ double huber_scale(double r0, double r1, double delta, double delta2, double& rho) {
+  const double n2 = __builtin_fma(r0, r0, r1 * r1);
+  const bool lin = n2 > delta2;
+  const double a = lin ? n2 : 1.0;
+  double q = rsq_nr(a);                                          // 1 / n
+  q = __builtin_fma(0.5 * q, __builtin_fma(-(a * q), q, 1.0), q);
+  const double n = a * q;
+  const double w = delta * q;                                    // s^2 = delta / n (< 1)
+  double p = rsq_nr(w);
+  p = __builtin_fma(0.5 * p, __builtin_fma(-(w * p), p, 1.0), p);
+  rho = lin ? __builtin_fma(2.0 * delta, n, -delta2) : n2;
+  return lin ? w * p : 1.0;
+}
+
 // v[lane] for a register array without a runtime index (a runtime index would
 // put the whole array in scratch memory).
 template <int N>

@@ -372,6 +372,7 @@ void BAPlan::reset() {
                   &prof_first, &prof_off, &prof_last, &prof_src_ptr, &prof_src, &camb_ptr, &camb_src, &solve_tab})
     v->clear();
   obs_uv.clear();
+  obs_order.clear();
   te_lcam.clear();
   chunk_img.clear();
   pair_list.clear();
@@ -421,7 +422,7 @@ std::string build_plan(BAPlan& P, int N, int L, int M, int n_fixed, const int32_
 #else
   auto sub = [](const char*) {};
 #endif
-  PlanArr<int32_t>& sorted = P.scr_sorted;
+  PlanArr<int32_t>& sorted = P.obs_order;  // kept: internal position -> caller observation
   sized(sorted, std::max(M, 1));
   // Landmarks ordered by first camera (stable counting sort; no observation: last), which
   // keeps each workgroup's camera window narrow, and their observations grouped by (landmark,

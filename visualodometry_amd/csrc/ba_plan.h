@@ -226,6 +226,11 @@ struct BAPlan {
   // observations in internal order (points by first camera, then camera)
   PlanArr<float> obs_uv;      // 2 per obs
   PlanArr<int32_t> obs_cam, obs_te;
+  // internal observation position -> the caller's (problem-order) observation index: written in
+  // full by every build_plan (the landmark ordering pass), part of the plan's result and read
+  // after planning -- the residual read-out (ba_engine.hip residuals()) maps its problem-order
+  // arrays through it.  Not digested (plan_digest pins the arrays the kernels read).
+  PlanArr<int32_t> obs_order;
   // track entries
   PlanArr<int32_t> te_cam, te_pt, te_obs;  // te_obs: n_te+1
   PlanArr<int16_t> te_lcam;                    // segment-local free camera, -1 if fixed
@@ -284,7 +289,6 @@ struct BAPlan {
   // refuse such a plan (host-only plans, digests and probes, always copy the images).
   bool host_images_partial = false;
   // planner scratch (never digested; kept across plans so a session's next window reuses it)
-  PlanArr<int32_t> scr_sorted;
   std::shared_ptr<PlanScratch> scratch;  // the planner's working containers (ba_plan.cpp)
 
   BAPlan() = default;

@@ -49,6 +49,7 @@ class VOConfig:
     ba_fixed: int = 2  # oldest keyframes held fixed (gauge)
     ba_iters: int = 10  # Gauss-Newton iterations per keyframe
     ba_lambda: float = 1.0  # fixed Levenberg damping (identical in oracle and kernel)
+    ba_huber: float = 0.0  # Huber delta of the BA cost in pixels; 0: plain sum of squares
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)
