@@ -196,7 +196,8 @@ int vo_ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_f
  * points: (n_points, 3) float64 -- the sizes of the session's problem. */
 int vo_ba_set_state(vo_ctx* ctx, uint64_t session, const double* poses, const double* points);
 int vo_ba_get_state(vo_ctx* ctx, uint64_t session, double* poses, double* points);
-/* Runs `iters` pure Gauss-Newton iterations (every step accepted) on the
+/* Runs `iters` pure Gauss-Newton iterations (every step accepted, the damping fixed at the
+ * problem's lambda; vo_ba_run_lm below is the variant that tests each step) on the
  * device-resident state.  cost_out (iters+1 doubles, may be NULL): sum of
  * squared residuals (of rho under vo_ba_set_robust) before each iteration and after the last one.
  * Returns VO_ERR_NOT_SPD (state left at the last good iterate) if the reduced
@@ -211,6 +212,46 @@ int vo_ba_run_async(vo_ctx* ctx, uint64_t session, int iters);
  * cost_out: 1 double.  The state is advanced by the step. */
 int vo_ba_gn_step(vo_ctx* ctx, uint64_t session, double* S_out, double* b_out, double* dc_out,
                   double* cost_out);
+/* Levenberg-Marquardt step control: `iters` trial steps, each kept only if it lowers the cost,
+ * with the damping adapted on the device (no host round trip per iteration).  With x the
+ * accepted state, c = cost(x) (sum ||r||^2, or sum rho under vo_ba_set_robust) and l the damping:
+ *   for k in 0 .. iters-1:
+ *     cost[k] = c; lambda[k] = l
+ *     x' = x (+) the step vo_ba_gn_step takes at x with the problem's lambda replaced by l
+ *     t = cost(x'); trial[k] = t
+ *     if t < c (false for NaN, +inf): x = x'; c = t; l = max(l * down, lambda_min); accepted[k] = 1
+ *     else:                                          l = min(l * up, lambda_max);   accepted[k] = 0
+ *   cost[iters] = c; lambda[iters] = l
+ * Every c and t is one kernel path's fixed-order sum, so cost[k+1] == trial[k] bit for bit after
+ * an accepted step; a rejected step restores poses and points bit for bit.  LM guarantees a
+ * non-increasing cost and needs no hand-tuned lambda; it does not promise a smaller error against
+ * ground truth than a heavily damped vo_ba_run (Step control).
+ * opt == NULL or a zero field takes the default: up 10, down 0.1, lambda_min 1e-6, lambda_max 1e6,
+ * lambda0 = the problem's lambda when that is > 0, else 1e-4; lambda0 is clamped into
+ * [lambda_min, lambda_max].  VO_ERR_ARG: a non-finite field, lambda0 < 0, up <= 1, down outside
+ * (0, 1), lambda_min <= 0, lambda_min > lambda_max.  VO_ERR_STATE: a stale session, or a
+ * communicator of more than one rank (LM over landmark shards is not built).  iters == 0 is
+ * legal: cost_out[0] is the cost, the state is untouched.  Outputs (any may be NULL): cost_out and
+ * lambda_out iters+1 doubles, trial_out iters doubles, accepted_out iters bytes.
+ * A non-SPD reduced system or a timed-out fused reduction fails the run as it fails vo_ba_run
+ * (VO_ERR_NOT_SPD / VO_ERR_HIP): the state is the last accepted one, cost and lambda of the
+ * failing iteration are its accepted state's, its trial and decision and every later entry are
+ * NaN / 0.  (A non-SPD system is not treated as a rejected step, and the loop never stops early.)
+ * A pending vo_ba_gn_step's landmark update is applied first, under the lambda and delta it was
+ * solved with; after the call no step is pending, and every other vo_ba_* call works as on any
+ * state. */
+typedef struct {
+  double lambda0, up, down, lambda_min, lambda_max;
+} vo_ba_lm_options;
+int vo_ba_run_lm(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_options* opt, double* cost_out,
+                 double* lambda_out, double* trial_out, uint8_t* accepted_out);
+/* Same, enqueued on the context stream with no host synchronisation and no read-back. */
+int vo_ba_run_lm_async(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_options* opt);
+/* Synchronises and returns the log of the session's last vo_ba_run_lm / _async: its first n
+ * iterations (n + 1 costs and lambdas, n trials and decisions; n at most that run's iters, else
+ * VO_ERR_ARG; any pointer may be NULL), and that run's return code. */
+int vo_ba_lm_log(vo_ctx* ctx, uint64_t session, int n, double* cost_out, double* lambda_out, double* trial_out,
+                 uint8_t* accepted_out);
 /* Robust cost: huber_delta = delta >= 0 in pixels, 0 (the default of every vo_ba_setup) is the
  * plain sum of squares.  For an observation with raw residual r, n^2 = r.r: n^2 <= delta^2 gives
  * rho = n^2; otherwise rho = 2 delta n - delta^2, and the linearisation scales r and both
@@ -264,7 +305,10 @@ int vo_ba_debug_stamps(vo_ctx* ctx, uint64_t* out, int n);
  *      17 pnp_decide, 18 pnp_hyp_tail, 19 pnp_score_tail (large batches: the replay after
  *      the first hypotheses of every frame, then the rest for the frames still looping),
  *      20 ess_hyp, 21 ess_score (both: the first slice and the rest), 22 ess_decide,
- *      23 ess_final, 24 ess_pose (essential-matrix initialisation). */
+ *      23 ess_final, 24 ess_pose (essential-matrix initialisation).
+ * vo_ba_run_lm's K1, K2 and K3 launches count under 0, 1 and 2 as vo_ba_run's do; its step
+ * decision (ba_lm_decide, which sums the cost partials in K2's order) counts under 1 too: with
+ * K2 fused into K3's launch, the default on one rank, it is the only launch there. */
 #define VO_PROFILE_KERNELS 25
 int vo_profile_enable(vo_ctx* ctx, int on);
 int vo_profile_read(vo_ctx* ctx, double* ms_out, int64_t* counts_out);

@@ -41,6 +41,12 @@ class VoError(RuntimeError):
         self.code = code
 
 
+class BALmOptionsC(C.Structure):
+    """``vo_ba_lm_options``: a zero field takes the library's default."""
+    _fields_ = [("lambda0", C.c_double), ("up", C.c_double), ("down", C.c_double),
+                ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
+
+
 class BAProblemC(C.Structure):
     _fields_ = [
         ("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32),
@@ -87,6 +93,9 @@ SIGNATURES = {
     "vo_ba_run": (_I, [_P, C.c_uint64, _I, _PD]),
     "vo_ba_run_async": (_I, [_P, C.c_uint64, _I]),
     "vo_ba_gn_step": (_I, [_P, C.c_uint64, _PD, _PD, _PD, _PD]),
+    "vo_ba_run_lm": (_I, [_P, C.c_uint64, _I, C.POINTER(BALmOptionsC), _PD, _PD, _PD, C.POINTER(C.c_uint8)]),
+    "vo_ba_run_lm_async": (_I, [_P, C.c_uint64, _I, C.POINTER(BALmOptionsC)]),
+    "vo_ba_lm_log": (_I, [_P, C.c_uint64, _I, _PD, _PD, _PD, C.POINTER(C.c_uint8)]),
     "vo_ba_set_robust": (_I, [_P, C.c_uint64, _D]),
     "vo_ba_residuals": (_I, [_P, C.c_uint64, _PD, _PD]),
     "vo_ba_solve": (_I, [_P, C.POINTER(BAProblemC), _PD, _PD, _I, _PD]),

@@ -20,6 +20,12 @@ observation's residual and Jacobians by ``sqrt(delta / ||r||)`` in the linearisa
 then ``sum rho``.  ``residuals()`` / ``optimize(..., return_residuals=True)`` give the raw squared
 reprojection error and depth per observation, so a caller can drop the tracks the solve ended
 up disagreeing with.
+
+Step control (off by default): ``lm=True`` (or ``cfg.ba_lm``) runs ``vo_ba_run_lm`` instead of the
+fixed-damping ``vo_ba_run``: each step is tried, kept only if the cost went down, and the damping
+is adapted (x0.1 / x10), all on the device; ``lam`` is then the starting damping.  It guarantees a
+non-increasing cost, not a smaller error against ground truth (``tests/ba_lm_ref.py`` restates the
+loop on the oracle).
 """
 
 from __future__ import annotations
@@ -29,7 +35,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BAProblemC, C, VoError, check, ptr
+from ._lib import BALmOptionsC, BAProblemC, C, VoError, check, ptr
 
 
 @dataclass
@@ -59,6 +65,10 @@ class BAResult:
     # depth per observation at the returned state, in the window's own observation order
     obs_err2: np.ndarray | None = None
     obs_depth: np.ndarray | None = None
+    # step control (lm=True): the damping before each trial and after the last, and each trial's
+    # verdict; cost_per_iter then holds the accepted-state costs
+    lambdas: np.ndarray | None = None
+    accepted: np.ndarray | None = None
 
 
 def poses_to_rt(poses_cw: np.ndarray) -> np.ndarray:
@@ -258,6 +268,43 @@ class BASession:
             check(rc, "vo_ba_run")
         return rc, costs
 
+    @staticmethod
+    def _lm_options(lam0, up, down, lam_min, lam_max) -> BALmOptionsC:
+        return BALmOptionsC(float(lam0), float(up), float(down), float(lam_min), float(lam_max))
+
+    def _lm_buffers(self, n: int):
+        n = max(n, 0)  # (a negative count is the library's to refuse)
+        return np.empty(n + 1), np.empty(n + 1), np.empty(n), np.empty(n, dtype=np.uint8)
+
+    def run_lm(self, iters: int, lam0: float = 0.0, up: float = 0.0, down: float = 0.0, lam_min: float = 0.0,
+               lam_max: float = 0.0):
+        """``iters`` Levenberg-Marquardt trial steps (``vo_ba_run_lm``; a zero option takes the
+        library's default); returns ``(status_code, costs[iters+1], lambdas[iters+1], trials[iters],
+        accepted[iters])``."""
+        costs, lambdas, trials, accepted = self._lm_buffers(int(iters))
+        opt = self._lm_options(lam0, up, down, lam_min, lam_max)
+        rc = self.ctx.lib.vo_ba_run_lm(self.ctx.handle, self.session, int(iters), C.byref(opt), ptr(costs, C.c_double),
+                                       ptr(lambdas, C.c_double), ptr(trials, C.c_double), ptr(accepted, C.c_uint8))
+        if rc not in (_lib.VO_OK, _lib.VO_ERR_NOT_SPD):
+            check(rc, "vo_ba_run_lm")
+        return rc, costs, lambdas, trials, accepted
+
+    def run_lm_async(self, iters: int, lam0: float = 0.0, up: float = 0.0, down: float = 0.0, lam_min: float = 0.0,
+                     lam_max: float = 0.0) -> None:
+        opt = self._lm_options(lam0, up, down, lam_min, lam_max)
+        check(self.ctx.lib.vo_ba_run_lm_async(self.ctx.handle, self.session, int(iters), C.byref(opt)),
+              "vo_ba_run_lm_async")
+
+    def lm_log(self, n: int):
+        """Synchronises; the first ``n`` iterations of the last ``run_lm`` / ``run_lm_async``'s log, as
+        ``run_lm`` returns it."""
+        costs, lambdas, trials, accepted = self._lm_buffers(int(n))
+        rc = self.ctx.lib.vo_ba_lm_log(self.ctx.handle, self.session, int(n), ptr(costs, C.c_double),
+                                       ptr(lambdas, C.c_double), ptr(trials, C.c_double), ptr(accepted, C.c_uint8))
+        if rc not in (_lib.VO_OK, _lib.VO_ERR_NOT_SPD):
+            check(rc, "vo_ba_lm_log")
+        return rc, costs, lambdas, trials, accepted
+
     def run_async(self, iters: int) -> None:
         check(self.ctx.lib.vo_ba_run_async(self.ctx.handle, self.session, int(iters)), "vo_ba_run_async")
 
@@ -297,14 +344,15 @@ class BASession:
 class SlidingWindowBA:
     """``SlidingWindowBA(K, cfg).optimize(window) -> BAResult``.
 
-    ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda`` / ``ba_huber``; any
-    missing knob takes the keyword default.  Degenerate windows come back with
+    ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda`` / ``ba_huber`` / ``ba_lm``; any
+    missing knob takes the keyword default.  ``lm`` (``cfg.ba_lm``): Levenberg-Marquardt step
+    control on the device, ``lam`` its starting damping.  Degenerate windows come back with
     ``status != "ok"`` instead of raising, so ``process_frame`` keeps the
     reference's print-and-continue failure style (``vo.py:240-245``).
     """
 
     def __init__(self, K, cfg=None, *, iters: int = 10, lam: float = 0.0, huber: float = 0.0,
-                 device: int | None = None):
+                 device: int | None = None, lm: bool = False):
         self.K = np.asarray(K, dtype=np.float64)
         self.iters = int(getattr(cfg, "ba_iters", iters))
         self.lam = float(getattr(cfg, "ba_lambda", lam))
@@ -313,6 +361,7 @@ class SlidingWindowBA:
         # library's VO_ERR_ARG to a skipped window)
         if not (np.isfinite(self.huber) and self.huber >= 0.0):
             raise ValueError(f"ba_huber must be finite and >= 0, got {self.huber}")
+        self.lm = bool(getattr(cfg, "ba_lm", lm))
         self.device = device
 
     def reserve(self, n_poses: int, n_points: int, obs_per_point: float = 5.0, n_fixed: int = 2) -> None:
@@ -337,7 +386,11 @@ class SlidingWindowBA:
             sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
                              huber=self.huber)
             sess.set_state(poses, pts)
-            rc, costs = sess.run(self.iters)
+            lambdas = accepted = None
+            if self.lm:
+                rc, costs, lambdas, _, accepted = sess.run_lm(self.iters, lam0=self.lam)
+            else:
+                rc, costs = sess.run(self.iters)
             P, X = sess.get_state()
             if return_residuals:
                 err2, depth = sess.residuals()
@@ -350,4 +403,4 @@ class SlidingWindowBA:
                 return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", str(e))
             raise
         status = "ok" if rc == _lib.VO_OK else "not_spd"
-        return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth)
+        return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth, lambdas=lambdas, accepted=accepted)

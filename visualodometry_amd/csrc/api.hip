@@ -744,6 +744,36 @@ int vo_ba_gn_step(vo_ctx* ctx, uint64_t session, double* S_out, double* b_out, d
   return g != VO_OK ? g : rc;
 }
 
+int vo_ba_run_lm(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_options* opt, double* cost_out,
+                 double* lambda_out, double* trial_out, uint8_t* accepted_out) {
+  int rc = VO_OK;
+  int g = guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    rc = vo::ba_run_lm(ctx, iters, opt, cost_out, lambda_out, trial_out, accepted_out, true);
+  });
+  return g != VO_OK ? g : rc;
+}
+
+int vo_ba_run_lm_async(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_options* opt) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_run_lm(ctx, iters, opt, nullptr, nullptr, nullptr, nullptr, false);
+  });
+}
+
+int vo_ba_lm_log(vo_ctx* ctx, uint64_t session, int n, double* cost_out, double* lambda_out, double* trial_out,
+                 uint8_t* accepted_out) {
+  int rc = VO_OK;
+  int g = guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    rc = vo::ba_lm_log(ctx, n, cost_out, lambda_out, trial_out, accepted_out);
+  });
+  return g != VO_OK ? g : rc;
+}
+
 int vo_ba_set_robust(vo_ctx* ctx, uint64_t session, double huber_delta) {
   return guarded([&] {
     vo::bind(ctx);

@@ -415,6 +415,9 @@ __global__ __launch_bounds__(kLinThreads, 3) void ba_lin_kernel(LinArgs A) {  //
   Stamper<kStamp> st;
   st.start();
   constexpr bool kRob = (MODE & kRobust) != 0;
+  // step control: the damping of this linearisation (or of the step being back-substituted) is
+  // on the device; every later read of A.lambda sees it
+  if constexpr ((MODE & kLm) != 0) A.lambda = *A.lm_lambda;
   const int seg = blockIdx.x, tid = threadIdx.x;
   // one load level: the status word, the segment header (uniform) and this thread's
   // camera ids (fixed offsets in the header); then poses and the pending update
@@ -1011,6 +1014,7 @@ template <int MODE, bool kStamp, int NW>
 __global__ __launch_bounds__(kLinLanesWave * NW) void ba_lin_wave_kernel(LinArgs A) {
   constexpr bool kGroup = NW > 1;
   constexpr bool kRob = (MODE & kRobust) != 0;
+  if constexpr ((MODE & kLm) != 0) A.lambda = *A.lm_lambda;  // step control: the damping is on the device
   // the cross-chunk combine: its waves, whether they start before the late waves are done, and
   // a thread's 16-byte pieces of the slots' blocks and of the rhs
   constexpr int kCombWaves = NW < 4 ? NW : 4;
@@ -1848,10 +1852,15 @@ void set_solve_lds(int lds) {
   }
 }
 
+// the step-control (kLm) instantiations, launched from the end of this unit
+void launch_lin_lm(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream_t st);
+void launch_reduce_lm(const ReduceArgs& A, int workgroups, hipStream_t st);
+
 }  // namespace
 
 void launch_lin(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream_t st) {
   constexpr std::make_integer_sequence<int, kWaveMaxChunks> nws{};
+  if (mode & kLm) return launch_lin_lm(A, mode, wave_chunks, grid, st);
   switch (mode) {
     case kAccum: lin_launch<kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
     case kBacksub | kAccum: lin_launch<kBacksub | kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
@@ -1868,6 +1877,7 @@ void launch_lin(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream
 }
 
 void launch_reduce(const ReduceArgs& A, int workgroups, hipStream_t st) {
+  if (A.lm_lambda) return launch_reduce_lm(A, workgroups, st);
   hipLaunchKernelGGL(ba_reduce_kernel, dim3(workgroups), dim3(kRedThreads), 0, st, A);
 }
 
@@ -1891,6 +1901,148 @@ void launch_obs_residual(const ObsResidualArgs& A, hipStream_t st) {
   if (A.n_obs <= 0) return;
   hipLaunchKernelGGL(ba_obs_residual_kernel<kThreads>, dim3((A.n_obs + kThreads - 1) / kThreads), dim3(kThreads), 0,
                      st, A);
+}
+
+// ---- Levenberg-Marquardt step control (vo_ba_run_lm, DESIGN.md §Step control) --------------
+// Everything below is emitted behind the kernels above (templates instantiated here), so those
+// keep their place in the code object (see the note at ba_obs_residual_kernel).
+namespace {
+
+// K2 with the camera damping read from the device (ReduceArgs::lm_lambda): ba_reduce_kernel's
+// loads, partition and summation order restated, as in the fused launch's reducers
+// (ba_band.hip band_reduce_wg), so all three give sys the same bits for the same damping.  A
+// kernel of its own, not a shared inlined body: with one, ba_reduce_kernel's code changed (its
+// status test went from a scalar to a vector load), and the GN path keeps its kernels as they are.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void ba_reduce_lm_kernel(ReduceArgs A) {
+  static_assert(kThreads == kRedThreads, "K2's partition");
+  __shared__ __attribute__((aligned(16))) double part[kRedSParts * 36];
+  __shared__ double partb[kRedBParts * 6];
+  const int blk = blockIdx.x, tid = threadIdx.x;
+  if (blk < A.nprof) {
+    const int4 m = A.meta[blk];
+    const int2 o = A.out[blk];
+    const int failed = A.status ? *A.status : 0;
+    const bool diag = m.z >= 0;
+    double2 ps = make_double2(0.0, 0.0);
+    double pb = 0.0;
+    if (tid < kRedSParts * 18) ps = sum_rows2(A.slab, m.x, m.y, tid / 18, kRedSParts, tid % 18);
+    if (diag && tid < kRedBParts * 6) pb = sum_rows<6>(A.slab_b, m.z, m.w, tid / 6, kRedBParts, tid % 6);
+    if (failed) return;  // uniform
+    if (tid < kRedSParts * 18) reinterpret_cast<double2*>(part)[tid] = ps;
+    if (tid < kRedBParts * 6) partb[tid] = pb;
+    __syncthreads();
+    if (tid < 36) {
+      double acc = 0.0;
+#pragma unroll
+      for (int q = 0; q < kRedSParts; ++q) acc += part[36 * q + tid];
+      if (diag && tid % 7 == 0) acc += *A.lm_lambda;
+      A.sys[(o.x & ~kRedTranspose) + ((o.x & kRedTranspose) ? 6 * (tid % 6) + tid / 6 : tid)] = acc;
+    } else if (diag && tid >= 64 && tid < 70) {  // another wave: the rhs sum beside the S sum
+      const int e = tid - 64;
+      double acc = 0.0;
+      for (int q = 0; q < kRedBParts; ++q) acc += partb[6 * q + e];
+      A.sys[o.y + e] = acc;
+    }
+    return;
+  }
+  // cost: fixed-order lane-strided partial sums, then a fixed tree over the 256 lanes
+  double c = 0.0;
+  if (A.nseg > 0) {  // lane-strided, in order, every load of a batch in flight (sum_rows)
+    for (int s = tid; s < A.nseg; s += 4 * kRedThreads) {
+      double v[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = A.slab_cost[min(s + i * kRedThreads, A.nseg - 1)];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c += s + i * kRedThreads < A.nseg ? v[i] : 0.0;
+    }
+  }
+  if (A.status && *A.status) return;
+  __shared__ double cpart[kRedThreads];
+  cpart[tid] = c;
+  __syncthreads();
+  for (int m = kRedThreads / 2; m > 0; m >>= 1) {
+    if (tid < m) cpart[tid] += cpart[tid + m];
+    __syncthreads();
+  }
+  if (tid == 0) A.sys[A.cost_off] = cpart[0];
+}
+
+// The decision of one trial step (LmDecideArgs, ba_kernels.h).  The cost is summed exactly as
+// K2's cost item sums it (lane-strided batches of four, then the tree over kRedThreads lanes), in
+// every workgroup, so all of them hold the same bits and the same decision without a hand-off;
+// the log entries read (k) and written (k + 1; trial and accepted at k) are different words.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void ba_lm_decide_kernel(LmDecideArgs A) {
+  static_assert(kThreads == kRedThreads, "K2's cost order");
+  __shared__ double cpart[kThreads];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int i = tid; i < A.nseg; i += 4 * kThreads) {
+    double v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = A.slab_cost[min(i + u * kThreads, A.nseg - 1)];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s += i + u * kThreads < A.nseg ? v[u] : 0.0;
+  }
+  if (*A.status) return;  // a failed solve: the state stays the last accepted one (uniform)
+  cpart[tid] = s;
+  __syncthreads();
+  for (int m = kThreads / 2; m > 0; m >>= 1) {
+    if (tid < m) cpart[tid] += cpart[tid + m];
+    __syncthreads();
+  }
+  const double t = cpart[0];
+  const bool init = A.k < 0;
+  const double c = init ? 0.0 : A.cost[A.k];
+  const double lam = init ? A.lambda0 : A.lambda[A.k];
+  const bool acc = init || t < c;  // false for a NaN or +inf trial cost
+  // accepted: the landmarks become the snapshot; rejected: they and the poses are restored
+  const long n = 3l * A.n_points, stride = (long)gridDim.x * kThreads, i0 = (long)blockIdx.x * kThreads + tid;
+  const double* src = acc ? A.points : A.snap;
+  double* dst = acc ? A.snap : A.points;
+  for (long i = i0; i < n; i += stride) dst[i] = src[i];
+  if (!acc)
+    for (long i = i0; i < 12l * A.n_poses; i += stride) A.pose_next[i] = A.pose_cur[i];
+  if (blockIdx.x == 0 && tid == 0) {
+    if (init) {
+      A.cost[0] = t;
+      A.lambda[0] = lam;
+    } else {
+      double l = lam * (acc ? A.down : A.up);
+      if (acc && l < A.lambda_min) l = A.lambda_min;
+      if (!acc && l > A.lambda_max) l = A.lambda_max;
+      A.trial[A.k] = t;
+      A.accepted[A.k] = acc ? 1 : 0;
+      A.cost[A.k + 1] = acc ? t : c;
+      A.lambda[A.k + 1] = l;
+    }
+  }
+}
+
+void launch_lin_lm(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream_t st) {
+  constexpr std::make_integer_sequence<int, kWaveMaxChunks> nws{};
+  switch (mode) {
+    case kLm | kAccum: lin_launch<kLm | kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
+    case kLm | kBacksub: lin_launch<kLm | kBacksub>(A, wave_chunks, dim3(grid), st, nws); break;
+    case kLm | kRobust | kAccum: lin_launch<kLm | kRobust | kAccum>(A, wave_chunks, dim3(grid), st, nws); break;
+    case kLm | kRobust | kBacksub: lin_launch<kLm | kRobust | kBacksub>(A, wave_chunks, dim3(grid), st, nws); break;
+    default: VO_REQUIRE(false, VO_ERR_STATE, "K1: no step-control instantiation of mode %d", mode);
+  }
+}
+
+void launch_reduce_lm(const ReduceArgs& A, int workgroups, hipStream_t st) {
+  hipLaunchKernelGGL(ba_reduce_lm_kernel<kRedThreads>, dim3(workgroups), dim3(kRedThreads), 0, st, A);
+}
+
+}  // namespace
+
+int lm_decide_grid(int n_points) {
+  return (int)std::min<long>(128, std::max<long>(1, (3l * n_points + 4 * kRedThreads - 1) / (4 * kRedThreads)));
+}
+
+void launch_lm_decide(const LmDecideArgs& A, hipStream_t st) {
+  hipLaunchKernelGGL(ba_lm_decide_kernel<kRedThreads>, dim3(lm_decide_grid(A.n_points)), dim3(kRedThreads), 0, st, A);
 }
 
 }  // namespace vo

@@ -221,6 +221,8 @@ __device__ __forceinline__ void st_sc1(double* p, double v) {
                      __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// kLm (step control, vo_ba_run_lm): the camera damping comes from the device (ReduceArgs::lm_lambda).
+template <bool kLm>
 __device__ __forceinline__ void band_reduce_wg(const BandArgs& B, int r, double* scr) {
   static_assert(kRedThreads * kBandRedItems == 512, "two K2 items per 512-thread workgroup");
   const ReduceArgs& A = B.red;
@@ -271,7 +273,7 @@ __device__ __forceinline__ void band_reduce_wg(const BandArgs& B, int r, double*
       double acc = 0.0;
 #pragma unroll
       for (int q = 0; q < kRedSParts; ++q) acc += part[36 * q + t];
-      if (diag && t % 7 == 0) acc += A.lambda;
+      if (diag && t % 7 == 0) acc += kLm ? *A.lm_lambda : A.lambda;
       st_sc1(A.sys + (o.x & ~kRedTranspose) + ((o.x & kRedTranspose) ? 6 * (t % 6) + t / 6 : t), acc);
     } else if (diag && t >= 64 && t < 70) {
       const int e = t - 64;
@@ -380,7 +382,9 @@ __device__ __forceinline__ bool xch_flag_wait(const double* fac, long flag, unsi
 // sides' columns in LDS), 2 split (one workgroup of four waves per side, each side's columns in
 // its own CU's LDS; the separator's bottom contributions, the top's separator records and the
 // separator's z cross over through global memory once each: see the split hand-offs below).
-template <int kMode>
+// kLm: the fused launch of a step-control iteration (its reducers read the damping from the
+// device; full mode only, the one that fuses); the solver's code does not depend on it.
+template <int kMode, bool kLm = false>
 __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
   constexpr bool kFull = kMode != 0, kSplit = kMode == 2;
   constexpr int NT = kSplit ? kBandThreads / 2 : kBandThreads;  // threads of this workgroup
@@ -394,7 +398,7 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   // split mode: workgroup s is side s, its four waves the side's four roles
   if (A.nred > 0 && blockIdx.x > 0) {  // fused K2: a reducer workgroup (uniform branch)
-    band_reduce_wg(A, blockIdx.x - 1, dyn);
+    band_reduce_wg<kLm>(A, blockIdx.x - 1, dyn);
     return;
   }
   // CS: doubles per column (K2 layout, factor record; full mode: SS == CS); SS per slot (ring mode: whole 1 KiB
@@ -1343,7 +1347,8 @@ void band_set_attributes(const BandLds& L) {
   const int lds = (int)band_launch_lds(L, true);
   int cur = set.load(std::memory_order_relaxed);
   if (lds <= cur) return;
-  const void* fs[3] = {(const void*)ba_band_kernel<0>, (const void*)ba_band_kernel<1>, (const void*)ba_band_kernel<2>};
+  const void* fs[4] = {(const void*)ba_band_kernel<0>, (const void*)ba_band_kernel<1>, (const void*)ba_band_kernel<2>,
+                       (const void*)ba_band_kernel<1, true>};
   for (const void* f : fs) VO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   while (cur < lds && !set.compare_exchange_weak(cur, lds, std::memory_order_relaxed)) {
   }
@@ -1356,6 +1361,8 @@ void launch_band_solve(const BandArgs& A, const BandLds& L, hipStream_t st) {
   const size_t lds = band_launch_lds(L, A.nred > 0);
   if (L.split)  // one workgroup of four waves per side (K2 never fused: BAEngine::fused)
     hipLaunchKernelGGL((ba_band_kernel<2>), dim3(2), dim3(kBandThreads / 2), lds, st, A);
+  else if (L.full && A.nred > 0 && A.red.lm_lambda)  // step control: the reducers' damping is on the device
+    hipLaunchKernelGGL((ba_band_kernel<1, true>), grid, dim3(kBandThreads), lds, st, A);
   else if (L.full)
     hipLaunchKernelGGL((ba_band_kernel<1>), grid, dim3(kBandThreads), lds, st, A);
   else

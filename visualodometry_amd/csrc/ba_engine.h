@@ -17,6 +17,9 @@ void ba_set_state(vo_ctx* ctx, const double* poses, const double* pts);
 void ba_get_state(vo_ctx* ctx, double* poses, double* pts);
 int ba_run(vo_ctx* ctx, int iters, double* cost, bool sync);
 int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost);
+int ba_run_lm(vo_ctx* ctx, int iters, const vo_ba_lm_options* opt, double* cost, double* lambda, double* trial,
+              uint8_t* accepted, bool sync);
+int ba_lm_log(vo_ctx* ctx, int n, double* cost, double* lambda, double* trial, uint8_t* accepted);
 void ba_set_robust(vo_ctx* ctx, double huber_delta);
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
 int ba_stats(vo_ctx* ctx, int64_t* out, int n);

@@ -172,6 +172,7 @@ class BAEngine {
     pending_ = false;
     cur_ = 0;
     huber_ = 0.0;  // every problem starts with the plain cost
+    lm_iters_ = -1;  // and without an LM log
     obs_uploaded_ = false;
     session_ = ++g_ba_sessions;
     return session_;
@@ -215,6 +216,9 @@ class BAEngine {
     for (int k = 0; k < 2; ++k) setup(&pr);
     h_state_.reserve((3ull * n_points + 12ull * n_poses) * 8);
     d_cost_.reserve(64 * 8);
+    // step control (run_lm): the landmark snapshot and a log of up to 64 iterations
+    d_lm_snap_.reserve(24ull * n_points);
+    d_lm_log_.reserve(lm_log_bytes(64));
     VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
     plan_ok_ = false;  // nothing of the synthetic plan is taken over
     have_problem_ = false;
@@ -357,6 +361,111 @@ class BAEngine {
     return VO_OK;
   }
 
+  // Levenberg-Marquardt step control (include/vo_hip.h vo_ba_run_lm, DESIGN.md §Step control):
+  // iters trial steps enqueued on the stream, accepted or rejected on the device.  Per trial: K1
+  // accumulate, K2 + K3 (as a GN iteration, the damping read from the log's entry k), a
+  // back-substitute-only K1 that lands the landmark update and leaves the trial state's cost
+  // partials, and ba_lm_decide, after which the flipped pose buffer and the points hold the
+  // accepted state and no step is pending.  sync: reads the log back (lm_read).
+  int run_lm(int iters, const vo_ba_lm_options* opt, double* cost_out, double* lambda_out, double* trial_out,
+             uint8_t* accepted_out, bool sync) {
+    require_state();
+    VO_REQUIRE(iters >= 0, VO_ERR_ARG, "vo_ba_run_lm: iters < 0");
+    VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_run_lm: not with a communicator of more than one rank");
+    const vo_ba_lm_options o = lm_options(opt);
+    hipStream_t st = ctx_->stream;
+    apply_pending();  // a pending GN step: under the lambda and delta it was solved with
+    d_lm_log_.reserve(lm_log_bytes(iters));
+    d_lm_snap_.reserve(24ull * std::max(1, plan_.n_points));
+    lm_iters_ = iters;
+    lm_session_ = session_;
+    lm_unread_ = true;
+    lm_fail_ = 0;
+    lm_timeout_ = false;
+    LmDecideArgs D{};
+    D.nseg = std::max(1, plan_.n_segments());
+    D.n_points = plan_.n_points;
+    D.n_poses = plan_.n_poses;
+    D.lambda0 = o.lambda0; D.up = o.up; D.down = o.down; D.lambda_min = o.lambda_min; D.lambda_max = o.lambda_max;
+    D.slab_cost = d_slab_cost_.as<double>();
+    D.cost = d_lm_log_.as<double>();
+    D.lambda = D.cost + iters + 1;
+    D.trial = D.lambda + iters + 1;
+    D.accepted = reinterpret_cast<int*>(D.trial + iters);
+    D.points = d_points_.as<double>();
+    D.snap = d_lm_snap_.as<double>();
+    D.status = d_status_.as<int>();
+    auto decide = [&](int k) {
+      D.k = k;
+      D.pose_cur = d_pose_[cur_ ^ 1].as<double>();
+      D.pose_next = d_pose_[cur_].as<double>();
+      ctx_->prof.begin(st, kKBaReduce);  // (no id of its own: vo_hip.h, kernel timing)
+      launch_lm_decide(D, st);
+      ctx_->prof.end(st);
+      VO_HIP_CHECK(hipGetLastError());
+    };
+    enqueue_lin(0);  // the cost at the start state
+    decide(-1);
+    struct Scope {  // the kLm kernels only between here and the end of the loop
+      const double*& p;
+      ~Scope() { p = nullptr; }
+    } scope{lm_lambda_};
+    for (int k = 0; k < iters; ++k) {
+      lm_lambda_ = D.lambda + k;
+      enqueue_lin(kAccum);
+      enqueue_reduce();
+      enqueue_solve(k + 1);
+      cur_ ^= 1;
+      enqueue_lin(kBacksub);  // the trial landmarks, and the cost partials at the trial state
+      decide(k);
+    }
+    lm_lambda_ = nullptr;
+    if (!sync) return VO_OK;
+    return lm_read(iters, cost_out, lambda_out, trial_out, accepted_out, "vo_ba_run_lm");
+  }
+
+  // Synchronises and returns the first n iterations of the last run_lm's log.  A failed
+  // iteration f (non-SPD system or a timed-out fused reduction: run()'s contract) leaves the
+  // state at the last accepted one; its trial and decision and every later entry are NaN / 0.
+  int lm_read(int n, double* cost_out, double* lambda_out, double* trial_out, uint8_t* accepted_out,
+              const char* who) {
+    VO_REQUIRE(lm_iters_ >= 0 && lm_session_ == session_, VO_ERR_STATE, "%s: no vo_ba_run_lm on this session", who);
+    VO_REQUIRE(n >= 0 && n <= lm_iters_, VO_ERR_ARG, "%s: n = %d outside the last run's 0..%d iterations", who, n,
+               lm_iters_);
+    hipStream_t st = ctx_->stream;
+    const int N = lm_iters_;
+    std::vector<double> log(3 * (size_t)N + 2);
+    std::vector<int> acc(std::max(1, N));
+    int status = 0;
+    VO_HIP_CHECK(hipMemcpyAsync(log.data(), d_lm_log_.ptr, log.size() * 8, hipMemcpyDeviceToHost, st));
+    if (N)
+      VO_HIP_CHECK(hipMemcpyAsync(acc.data(), d_lm_log_.as<double>() + log.size(), N * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (lm_unread_) VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    if (lm_unread_) {
+      lm_timeout_ = clear_failure(status);
+      lm_fail_ = status;
+      lm_unread_ = false;
+    }
+    const double *cost = log.data(), *lam = cost + N + 1, *trial = lam + N + 1;
+    const int f = lm_fail_ ? lm_fail_ - 1 : N;  // first iteration without a verdict
+    for (int k = 0; k <= n; ++k) {
+      if (cost_out) cost_out[k] = k <= f ? cost[k] : NAN;
+      if (lambda_out) lambda_out[k] = k <= f ? lam[k] : NAN;
+    }
+    for (int k = 0; k < n; ++k) {
+      if (trial_out) trial_out[k] = k < f ? trial[k] : NAN;
+      if (accepted_out) accepted_out[k] = k < f && acc[k] ? 1 : 0;
+    }
+    VO_REQUIRE(!lm_timeout_, VO_ERR_HIP, "%s: fused reduction timed out at iteration %d (a reducer workgroup never arrived)",
+               who, lm_fail_ - 1);
+    if (lm_fail_) {
+      set_error("%s: reduced camera system not positive definite at iteration %d", who, lm_fail_ - 1);
+      return VO_ERR_NOT_SPD;
+    }
+    return VO_OK;
+  }
+
   // After a failed fused launch (any non-zero status; kBandStatusTimeout: the solver gave up
   // waiting for its reducers) the reducer counter is re-zeroed -- the stream is synchronised,
   // so every late reducer has counted itself by now -- and the timeout flag is stripped from
@@ -441,6 +550,30 @@ class BAEngine {
   void require_state() const {
     VO_REQUIRE(have_problem_, VO_ERR_STATE, "BA: no problem set up");
     VO_REQUIRE(have_state_, VO_ERR_STATE, "BA: no state set");
+  }
+
+  // The log of an LM run of n iterations: cost (n + 1), lambda (n + 1), trial (n) doubles, then
+  // the n decisions (ints).
+  static size_t lm_log_bytes(int n) { return (3 * (size_t)n + 2) * 8 + std::max(1, n) * sizeof(int); }
+
+  // vo_ba_run_lm's options with the defaults filled in (vo_hip.h); VO_ERR_ARG for a bad field.
+  vo_ba_lm_options lm_options(const vo_ba_lm_options* opt) const {
+    vo_ba_lm_options o = opt ? *opt : vo_ba_lm_options{};
+    VO_REQUIRE(std::isfinite(o.lambda0) && std::isfinite(o.up) && std::isfinite(o.down) &&
+                   std::isfinite(o.lambda_min) && std::isfinite(o.lambda_max),
+               VO_ERR_ARG, "vo_ba_run_lm: non-finite option");
+    if (o.up == 0.0) o.up = 10.0;
+    if (o.down == 0.0) o.down = 0.1;
+    if (o.lambda_min == 0.0) o.lambda_min = 1e-6;
+    if (o.lambda_max == 0.0) o.lambda_max = 1e6;
+    if (o.lambda0 == 0.0) o.lambda0 = prob_.lambda > 0.0 ? prob_.lambda : 1e-4;
+    VO_REQUIRE(o.lambda0 >= 0.0, VO_ERR_ARG, "vo_ba_run_lm: lambda0 < 0");
+    VO_REQUIRE(o.up > 1.0, VO_ERR_ARG, "vo_ba_run_lm: up must be > 1");
+    VO_REQUIRE(o.down > 0.0 && o.down < 1.0, VO_ERR_ARG, "vo_ba_run_lm: down must be in (0, 1)");
+    VO_REQUIRE(o.lambda_min > 0.0 && o.lambda_min <= o.lambda_max, VO_ERR_ARG,
+               "vo_ba_run_lm: need 0 < lambda_min <= lambda_max");
+    o.lambda0 = std::min(std::max(o.lambda0, o.lambda_min), o.lambda_max);
+    return o;
   }
 
   // ---- setup's steps, in its order ----------------------------------------------------------
@@ -703,6 +836,7 @@ class BAEngine {
     A.stamps = nullptr;
     A.huber = huber_;
     A.huber2 = huber_ * huber_;
+    A.lm_lambda = lm_lambda_;
     return A;
   }
 
@@ -734,6 +868,8 @@ class BAEngine {
       d_stamps_.reserve((size_t)plan_.n_chunks() * kPhCount * 8);
       A.stamps = d_stamps_.as<unsigned long long>();
     }
+    // inside an LM run (lm_lambda_ set) the modes that use the damping read it from the device
+    if (lm_lambda_ && mode != 0) mode |= kLm;
     launch_lin(A, huber_ > 0.0 ? mode | kRobust : mode, wave ? nw : 0, nseg, ctx_->stream);
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
@@ -759,6 +895,7 @@ class BAEngine {
     R.sys = d_sys_.as<double>();
     R.cost_off = cost_off_;
     R.status = d_status_.as<int>();
+    R.lm_lambda = lm_lambda_;
     return R;
   }
 
@@ -967,6 +1104,13 @@ class BAEngine {
   DevBuf d_points_, d_pose_[2], d_dc_, d_slab_, d_slab_b_, d_slab_cost_, d_sys_;
   DevBuf d_cost_, d_cost_tmp_;
   double huber_ = 0.0;  // Huber delta in pixels, 0: plain cost (set_robust)
+  // step control (run_lm): the damping's device address while an LM run enqueues its kernels
+  // (null otherwise: the GN kernels), the log and the landmark snapshot, and what lm_read needs
+  const double* lm_lambda_ = nullptr;
+  DevBuf d_lm_log_, d_lm_snap_;
+  int lm_iters_ = -1, lm_fail_ = 0;
+  uint64_t lm_session_ = 0;
+  bool lm_unread_ = false, lm_timeout_ = false;
   // residuals(): the problem-order observation arrays (uploaded on a session's first call) and
   // its output [err2 | depth]
   bool obs_uploaded_ = false;
@@ -990,6 +1134,13 @@ void ba_get_state(vo_ctx* ctx, double* poses, double* pts) { ba_engine(ctx)->get
 int ba_run(vo_ctx* ctx, int iters, double* cost, bool sync) { return ba_engine(ctx)->run(iters, cost, sync); }
 int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost) {
   return ba_engine(ctx)->gn_step(S, b, dc, cost);
+}
+int ba_run_lm(vo_ctx* ctx, int iters, const vo_ba_lm_options* opt, double* cost, double* lambda, double* trial,
+              uint8_t* accepted, bool sync) {
+  return ba_engine(ctx)->run_lm(iters, opt, cost, lambda, trial, accepted, sync);
+}
+int ba_lm_log(vo_ctx* ctx, int n, double* cost, double* lambda, double* trial, uint8_t* accepted) {
+  return ba_engine(ctx)->lm_read(n, cost, lambda, trial, accepted, "vo_ba_lm_log");
 }
 void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta); }
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }

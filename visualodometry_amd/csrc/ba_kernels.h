@@ -23,7 +23,10 @@ constexpr int kS3Count = 10;  // values of the profile K3's stamp row (ba.hip kS
 
 // K1 modes: back-substitute the pending step, linearise and accumulate the Schur blocks; kRobust
 // selects the Huber instantiations (LinArgs::huber > 0), the other four are the plain-cost kernels.
-enum { kBacksub = 1, kAccum = 2, kRobust = 4 };
+// kLm (Levenberg-Marquardt step control, vo_ba_run_lm): the damping is read from the device
+// (LinArgs::lm_lambda) instead of LinArgs::lambda; instantiated for the two modes the LM loop
+// needs it in, kAccum and kBacksub alone (the cost-only kernel uses no damping), plain and kRobust.
+enum { kBacksub = 1, kAccum = 2, kRobust = 4, kLm = 8 };
 
 struct LinArgs {
   int n_fixed;
@@ -44,12 +47,14 @@ struct LinArgs {
   unsigned long long* stamps;  // diagnostic build only: per segment phase cycles
   int nseg;                    // segments
   double huber, huber2;        // Huber delta (pixels) and delta^2; read by the kRobust modes only
+  const double* lm_lambda;     // the damping on the device; read by the kLm modes only
 };
 // One workgroup per segment (grid): the one-wave K1 of wave_chunks (1 .. kWaveMaxChunks) chunks
 // per segment, or the four-wave K1 (wave_chunks = 0).
 void launch_lin(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream_t st);
 
 // K2: nprof + 1 workgroups (the last sums the cost), or 1 with nprof = 0: the cost alone.
+// (A.lm_lambda set: the instantiation that reads the camera damping from the device)
 void launch_reduce(const ReduceArgs& A, int workgroups, hipStream_t st);
 
 // K3: profile Cholesky solve S dc = b + pose update.
@@ -104,6 +109,29 @@ struct ObsResidualArgs {
   double* depth;          // n_obs out
 };
 void launch_obs_residual(const ObsResidualArgs& A, hipStream_t st);
+
+// Step control of vo_ba_run_lm (ba_lm_decide_kernel), one launch per trial step.  Every workgroup
+// sums the trial state's cost partials (slab_cost, K2's cost order) and takes the same decision
+// from the log's entries of iteration k, which no workgroup of the launch writes: accepted
+// (t < c) the points become the new snapshot, rejected they are restored from it and pose_next
+// (the trial poses) is overwritten with pose_cur; workgroup 0 appends entry k + 1 to the log.
+// k < 0: the initial cost, lambda0 and the first snapshot.  Nothing is written once *status is set.
+struct LmDecideArgs {
+  int k, nseg, n_points, n_poses;
+  double lambda0, up, down, lambda_min, lambda_max;
+  const double* slab_cost;
+  double* cost;        // log: accepted-state cost, iters + 1
+  double* lambda;      // log: damping, iters + 1 (entry k is what iteration k's kernels read)
+  double* trial;       // log: trial cost, iters
+  int* accepted;       // log: decision, iters
+  double* points;      // 3 per landmark: the trial state's on entry, the accepted state's on exit
+  double* snap;        // the accepted state's landmarks
+  const double* pose_cur;  // the accepted poses
+  double* pose_next;       // the trial poses
+  const int* status;
+};
+int lm_decide_grid(int n_points);
+void launch_lm_decide(const LmDecideArgs& A, hipStream_t st);
 
 // Runs of consecutive chunk images copied from the previous plan's device images (ba.hip
 // ba_img_copy_kernel); they travel in the arguments.

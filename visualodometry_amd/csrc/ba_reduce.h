@@ -22,6 +22,7 @@ struct ReduceArgs {
   double* sys;         // output: profile [S | b | cost] or the banded K3's column layout
   long cost_off;       // output offset of the cost
   const int* status;
+  const double* lm_lambda;  // vo_ba_run_lm: the damping on the device, read instead of lambda by the kLm reducers only
 };
 constexpr int kRedTranspose = 1 << 30;  // dst flag: store the block transposed
 

@@ -48,8 +48,9 @@ class VOConfig:
     ba_window: int = 50  # keyframes in the window
     ba_fixed: int = 2  # oldest keyframes held fixed (gauge)
     ba_iters: int = 10  # Gauss-Newton iterations per keyframe
-    ba_lambda: float = 1.0  # fixed Levenberg damping (identical in oracle and kernel)
+    ba_lambda: float = 1.0  # Levenberg damping: fixed (ba_lm off), or the starting value of the LM schedule
     ba_huber: float = 0.0  # Huber delta of the BA cost in pixels; 0: plain sum of squares
+    ba_lm: bool = False  # Levenberg-Marquardt step control on the device (accept / reject, adaptive damping)
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)
