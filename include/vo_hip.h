@@ -236,7 +236,8 @@ int vo_ba_gn_step(vo_ctx* ctx, uint64_t session, double* S_out, double* b_out, d
  * A non-SPD reduced system or a timed-out fused reduction fails the run as it fails vo_ba_run
  * (VO_ERR_NOT_SPD / VO_ERR_HIP): the state is the last accepted one, cost and lambda of the
  * failing iteration are its accepted state's, its trial and decision and every later entry are
- * NaN / 0.  (A non-SPD system is not treated as a rejected step, and the loop never stops early.)
+ * NaN / 0.  (A non-SPD system is not treated as a rejected step.  The loop runs every trial unless
+ * vo_ba_set_lm_stop below gave it a termination criterion.)
  * A pending vo_ba_gn_step's landmark update is applied first, under the lambda and delta it was
  * solved with; after the call no step is pending, and every other vo_ba_* call works as on any
  * state. */
@@ -252,6 +253,40 @@ int vo_ba_run_lm_async(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_
  * VO_ERR_ARG; any pointer may be NULL), and that run's return code. */
 int vo_ba_lm_log(vo_ctx* ctx, uint64_t session, int n, double* cost_out, double* lambda_out, double* trial_out,
                  uint8_t* accepted_out);
+/* Termination of the LM loop, decided on the device (still one fixed launch sequence and no host
+ * round trip per iteration).  With rej the number of consecutive rejections, 0 at the start of each
+ * run, three tests follow the decision of trial k (c = cost[k], t = trial[k], in doubles):
+ *   accepted:  rej = 0
+ *              if ftol > 0 and (c - t) <= ftol * c:        stop, VO_BA_LM_FTOL
+ *              else if xtol > 0 and max_i |dc_i| <= xtol:  stop, VO_BA_LM_XTOL   (dc: the 6F entries of
+ *                                                                                 trial k's pose update)
+ *   rejected:  rej += 1
+ *              if max_rejects > 0 and rej >= max_rejects:  stop, VO_BA_LM_REJECTS
+ * A stop at trial k ends the run with trials = k + 1; a run that never stops has trials = iters and
+ * VO_BA_LM_RAN_ALL.  A stop changes nothing before it: log entries 0 .. k (cost and lambda to
+ * k + 1), poses and points are bit for bit those of vo_ba_run_lm(iters = k + 1) with no criterion
+ * set.  The trials behind a stop are still enqueued, but their kernels leave at their first test
+ * of the status word; their log entries read trial = NaN, accepted = 0, and cost and lambda repeat
+ * entry k + 1, so cost_out[iters] is the final cost whether or not the run stopped.  A stopped run
+ * returns VO_OK and leaves nothing behind: the next vo_ba_run* call on the session, synchronous or
+ * not, needs no read in between.
+ * vo_ba_set_lm_stop: session state like vo_ba_set_robust, for every later vo_ba_run_lm / _async.
+ * stop == NULL or all fields zero: never stop, the state after every vo_ba_setup.  VO_ERR_ARG: a
+ * non-finite or negative field, ftol >= 1, reserved != 0.  VO_ERR_STATE: a stale session.
+ * vo_ba_lm_stop_info: synchronises as vo_ba_lm_log does and reports how the session's last LM run
+ * ended (either pointer may be NULL).  After a failed run (non-SPD or timeout, above): trials = the
+ * failing iteration's index, reason = VO_BA_LM_FAILED.  VO_ERR_STATE: no LM run on this session. */
+typedef struct {
+  double ftol, xtol;
+  int32_t max_rejects, reserved;
+} vo_ba_lm_stop;
+#define VO_BA_LM_FAILED (-1)
+#define VO_BA_LM_RAN_ALL 0
+#define VO_BA_LM_FTOL 1
+#define VO_BA_LM_XTOL 2
+#define VO_BA_LM_REJECTS 3
+int vo_ba_set_lm_stop(vo_ctx* ctx, uint64_t session, const vo_ba_lm_stop* stop);
+int vo_ba_lm_stop_info(vo_ctx* ctx, uint64_t session, int32_t* trials_out, int32_t* reason_out);
 /* Robust cost: huber_delta = delta >= 0 in pixels, 0 (the default of every vo_ba_setup) is the
  * plain sum of squares.  For an observation with raw residual r, n^2 = r.r: n^2 <= delta^2 gives
  * rho = n^2; otherwise rho = 2 delta n - delta^2, and the linearisation scales r and both

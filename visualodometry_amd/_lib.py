@@ -47,6 +47,17 @@ class BALmOptionsC(C.Structure):
                 ("lambda_min", C.c_double), ("lambda_max", C.c_double)]
 
 
+class BALmStopC(C.Structure):
+    """``vo_ba_lm_stop``: the LM loop's termination criteria; a zero field is not tested."""
+    _fields_ = [("ftol", C.c_double), ("xtol", C.c_double), ("max_rejects", C.c_int32), ("reserved", C.c_int32)]
+
+
+# vo_ba_lm_stop_info's reasons (VO_BA_LM_*)
+BA_LM_FAILED, BA_LM_RAN_ALL, BA_LM_FTOL, BA_LM_XTOL, BA_LM_REJECTS = -1, 0, 1, 2, 3
+BA_LM_REASONS = {BA_LM_FAILED: "failed", BA_LM_RAN_ALL: "ran_all", BA_LM_FTOL: "ftol", BA_LM_XTOL: "xtol",
+                 BA_LM_REJECTS: "rejects"}
+
+
 class BAProblemC(C.Structure):
     _fields_ = [
         ("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32),
@@ -96,6 +107,8 @@ SIGNATURES = {
     "vo_ba_run_lm": (_I, [_P, C.c_uint64, _I, C.POINTER(BALmOptionsC), _PD, _PD, _PD, C.POINTER(C.c_uint8)]),
     "vo_ba_run_lm_async": (_I, [_P, C.c_uint64, _I, C.POINTER(BALmOptionsC)]),
     "vo_ba_lm_log": (_I, [_P, C.c_uint64, _I, _PD, _PD, _PD, C.POINTER(C.c_uint8)]),
+    "vo_ba_set_lm_stop": (_I, [_P, C.c_uint64, C.POINTER(BALmStopC)]),
+    "vo_ba_lm_stop_info": (_I, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vo_ba_set_robust": (_I, [_P, C.c_uint64, _D]),
     "vo_ba_residuals": (_I, [_P, C.c_uint64, _PD, _PD]),
     "vo_ba_solve": (_I, [_P, C.POINTER(BAProblemC), _PD, _PD, _I, _PD]),

@@ -25,7 +25,9 @@ Step control (off by default): ``lm=True`` (or ``cfg.ba_lm``) runs ``vo_ba_run_l
 fixed-damping ``vo_ba_run``: each step is tried, kept only if the cost went down, and the damping
 is adapted (x0.1 / x10), all on the device; ``lam`` is then the starting damping.  It guarantees a
 non-increasing cost, not a smaller error against ground truth (``tests/ba_lm_ref.py`` restates the
-loop on the oracle).
+loop on the oracle).  ``lm_ftol`` / ``lm_xtol`` / ``lm_max_rejects`` (``cfg.ba_lm_*``) end the loop
+on the device once it has converged or keeps rejecting (``vo_ba_set_lm_stop``;
+``tests/ba_lm_stop_ref.py``); ``BAResult.lm_trials`` / ``lm_stop`` say how it ended.
 """
 
 from __future__ import annotations
@@ -35,7 +37,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BALmOptionsC, BAProblemC, C, VoError, check, ptr
+from ._lib import BALmOptionsC, BALmStopC, BAProblemC, C, VoError, check, ptr
 
 
 @dataclass
@@ -69,6 +71,10 @@ class BAResult:
     # verdict; cost_per_iter then holds the accepted-state costs
     lambdas: np.ndarray | None = None
     accepted: np.ndarray | None = None
+    # how the LM loop ended (None without lm): the trials that ran, and "ran_all", or the
+    # termination criterion that stopped it: "ftol", "xtol", "rejects"
+    lm_trials: int | None = None
+    lm_stop: str | None = None
 
 
 def poses_to_rt(poses_cw: np.ndarray) -> np.ndarray:
@@ -305,6 +311,21 @@ class BASession:
             check(rc, "vo_ba_lm_log")
         return rc, costs, lambdas, trials, accepted
 
+    def set_lm_stop(self, ftol: float = 0.0, xtol: float = 0.0, max_rejects: int = 0) -> None:
+        """Termination criteria of the later ``run_lm`` / ``run_lm_async`` calls (``vo_ba_set_lm_stop``):
+        a relative cost decrease of at most ``ftol``, a largest pose-update entry of at most ``xtol``,
+        ``max_rejects`` rejections in a row; a zero is not tested, all zero never stops."""
+        stop = BALmStopC(float(ftol), float(xtol), int(max_rejects), 0)
+        check(self.ctx.lib.vo_ba_set_lm_stop(self.ctx.handle, self.session, C.byref(stop)), "vo_ba_set_lm_stop")
+
+    def lm_stop_info(self):
+        """Synchronises; ``(trials, reason)`` of the last LM run: the trials that ran before it
+        ended and one of ``_lib.BA_LM_*`` (``vo_ba_lm_stop_info``)."""
+        trials, reason = C.c_int32(0), C.c_int32(0)
+        check(self.ctx.lib.vo_ba_lm_stop_info(self.ctx.handle, self.session, C.byref(trials), C.byref(reason)),
+              "vo_ba_lm_stop_info")
+        return int(trials.value), int(reason.value)
+
     def run_async(self, iters: int) -> None:
         check(self.ctx.lib.vo_ba_run_async(self.ctx.handle, self.session, int(iters)), "vo_ba_run_async")
 
@@ -346,13 +367,16 @@ class SlidingWindowBA:
 
     ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda`` / ``ba_huber`` / ``ba_lm``; any
     missing knob takes the keyword default.  ``lm`` (``cfg.ba_lm``): Levenberg-Marquardt step
-    control on the device, ``lam`` its starting damping.  Degenerate windows come back with
+    control on the device, ``lam`` its starting damping, ``lm_ftol`` / ``lm_xtol`` / ``lm_max_rejects``
+    (``cfg.ba_lm_ftol`` / ``ba_lm_xtol`` / ``ba_lm_max_rejects``, all 0: off) its termination
+    criteria.  Degenerate windows come back with
     ``status != "ok"`` instead of raising, so ``process_frame`` keeps the
     reference's print-and-continue failure style (``vo.py:240-245``).
     """
 
     def __init__(self, K, cfg=None, *, iters: int = 10, lam: float = 0.0, huber: float = 0.0,
-                 device: int | None = None, lm: bool = False):
+                 device: int | None = None, lm: bool = False, lm_ftol: float = 0.0, lm_xtol: float = 0.0,
+                 lm_max_rejects: int = 0):
         self.K = np.asarray(K, dtype=np.float64)
         self.iters = int(getattr(cfg, "ba_iters", iters))
         self.lam = float(getattr(cfg, "ba_lambda", lam))
@@ -362,6 +386,13 @@ class SlidingWindowBA:
         if not (np.isfinite(self.huber) and self.huber >= 0.0):
             raise ValueError(f"ba_huber must be finite and >= 0, got {self.huber}")
         self.lm = bool(getattr(cfg, "ba_lm", lm))
+        # termination of the LM loop (used with lm only); all zero: every trial runs
+        self.lm_ftol = float(getattr(cfg, "ba_lm_ftol", lm_ftol))
+        self.lm_xtol = float(getattr(cfg, "ba_lm_xtol", lm_xtol))
+        self.lm_max_rejects = int(getattr(cfg, "ba_lm_max_rejects", lm_max_rejects))
+        if not (0.0 <= self.lm_ftol < 1.0 and np.isfinite(self.lm_xtol) and self.lm_xtol >= 0.0
+                and self.lm_max_rejects >= 0):
+            raise ValueError("ba_lm_ftol must be in [0, 1), ba_lm_xtol finite and >= 0, ba_lm_max_rejects >= 0")
         self.device = device
 
     def reserve(self, n_poses: int, n_points: int, obs_per_point: float = 5.0, n_fixed: int = 2) -> None:
@@ -386,9 +417,13 @@ class SlidingWindowBA:
             sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
                              huber=self.huber)
             sess.set_state(poses, pts)
-            lambdas = accepted = None
+            lambdas = accepted = lm_trials = lm_stop = None
             if self.lm:
+                if self.lm_ftol or self.lm_xtol or self.lm_max_rejects:
+                    sess.set_lm_stop(self.lm_ftol, self.lm_xtol, self.lm_max_rejects)
                 rc, costs, lambdas, _, accepted = sess.run_lm(self.iters, lam0=self.lam)
+                lm_trials, reason = sess.lm_stop_info()
+                lm_stop = _lib.BA_LM_REASONS[reason]
             else:
                 rc, costs = sess.run(self.iters)
             P, X = sess.get_state()
@@ -403,4 +438,5 @@ class SlidingWindowBA:
                 return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", str(e))
             raise
         status = "ok" if rc == _lib.VO_OK else "not_spd"
-        return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth, lambdas=lambdas, accepted=accepted)
+        return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth, lambdas=lambdas, accepted=accepted,
+                        lm_trials=lm_trials, lm_stop=lm_stop)

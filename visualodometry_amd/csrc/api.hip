@@ -774,6 +774,22 @@ int vo_ba_lm_log(vo_ctx* ctx, uint64_t session, int n, double* cost_out, double*
   return g != VO_OK ? g : rc;
 }
 
+int vo_ba_set_lm_stop(vo_ctx* ctx, uint64_t session, const vo_ba_lm_stop* stop) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_set_lm_stop(ctx, stop);
+  });
+}
+
+int vo_ba_lm_stop_info(vo_ctx* ctx, uint64_t session, int32_t* trials_out, int32_t* reason_out) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_lm_stop_info(ctx, trials_out, reason_out);
+  });
+}
+
 int vo_ba_set_robust(vo_ctx* ctx, uint64_t session, double huber_delta) {
   return guarded([&] {
     vo::bind(ctx);

@@ -1972,7 +1972,8 @@ __global__ __launch_bounds__(kThreads) void ba_reduce_lm_kernel(ReduceArgs A) {
 // K2's cost item sums it (lane-strided batches of four, then the tree over kRedThreads lanes), in
 // every workgroup, so all of them hold the same bits and the same decision without a hand-off;
 // the log entries read (k) and written (k + 1; trial and accepted at k) are different words.
-template <int kThreads>
+// kStop: the termination tests in workgroup 0 (LmDecideArgs); without it, the loop that never stops.
+template <int kThreads, bool kStop>
 __global__ __launch_bounds__(kThreads) void ba_lm_decide_kernel(LmDecideArgs A) {
   static_assert(kThreads == kRedThreads, "K2's cost order");
   __shared__ double cpart[kThreads];
@@ -1985,7 +1986,13 @@ __global__ __launch_bounds__(kThreads) void ba_lm_decide_kernel(LmDecideArgs A) 
 #pragma unroll
     for (int u = 0; u < 4; ++u) s += i + u * kThreads < A.nseg ? v[u] : 0.0;
   }
-  if (*A.status) return;  // a failed solve: the state stays the last accepted one (uniform)
+  if constexpr (kStop) {
+    // this launch's own stop (workgroup 0 was faster) is no earlier failure: the copies are made
+    const int w = *A.status;
+    if (w != 0 && w != (kLmStatusStopped | (A.k + 1))) return;
+  } else {
+    if (*A.status) return;  // a failed solve: the state stays the last accepted one (uniform)
+  }
   cpart[tid] = s;
   __syncthreads();
   for (int m = kThreads / 2; m > 0; m >>= 1) {
@@ -2018,6 +2025,51 @@ __global__ __launch_bounds__(kThreads) void ba_lm_decide_kernel(LmDecideArgs A) 
       A.lambda[A.k + 1] = l;
     }
   }
+  if constexpr (kStop) {
+    if (blockIdx.x != 0) return;
+    if (init) {
+      if (tid == 0) A.stop[0] = A.stop[1] = 0;
+      return;
+    }
+    int reason = kLmRanAll;  // (every branch below is uniform over the workgroup)
+    if (acc) {
+      if (A.ftol > 0.0 && (c - t) <= A.ftol * c) {
+        reason = kLmFtol;
+      } else if (A.xtol > 0.0) {
+        double m = 0.0;
+        for (int i = tid; i < A.n_dc; i += kThreads) m = fmax(m, fabs(A.dc[i]));
+        __syncthreads();  // every thread has read the cost sum
+        cpart[tid] = m;
+        __syncthreads();
+        for (int h = kThreads / 2; h > 0; h >>= 1) {
+          if (tid < h) cpart[tid] = fmax(cpart[tid], cpart[tid + h]);
+          __syncthreads();
+        }
+        if (cpart[0] <= A.xtol) reason = kLmXtol;
+      }
+    } else if (A.max_rejects > 0) {
+      // consecutive rejections, this one included: the decisions earlier launches logged
+      int rej = 1;
+      for (int j = A.k - 1; j >= 0 && rej < A.max_rejects && A.accepted[j] == 0; --j) ++rej;
+      if (rej >= A.max_rejects) reason = kLmRejects;
+    }
+    if (tid == 0 && reason != kLmRanAll) {
+      A.stop[0] = A.k + 1;
+      A.stop[1] = reason;
+      *A.status = kLmStatusStopped | (A.k + 1);
+    }
+  }
+}
+
+// End of a run with a termination criterion: a status word that is exactly a stop word goes back
+// to zero, so the next run starts as after any successful one; a failure tag, or a stop word a
+// later fused launch added its timeout flag to, stays for the host to report.  (A template only so
+// that it is emitted where it is instantiated, behind every earlier kernel of the code object.)
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void ba_lm_finish_kernel(int* status) {
+  if (threadIdx.x != 0) return;
+  const int w = *status;
+  if ((w & ~(kLmStatusStopped - 1)) == kLmStatusStopped) *status = 0;  // the flag and a trial count below it
 }
 
 void launch_lin_lm(const LinArgs& A, int mode, int wave_chunks, int grid, hipStream_t st) {
@@ -2041,8 +2093,14 @@ int lm_decide_grid(int n_points) {
   return (int)std::min<long>(128, std::max<long>(1, (3l * n_points + 4 * kRedThreads - 1) / (4 * kRedThreads)));
 }
 
-void launch_lm_decide(const LmDecideArgs& A, hipStream_t st) {
-  hipLaunchKernelGGL(ba_lm_decide_kernel<kRedThreads>, dim3(lm_decide_grid(A.n_points)), dim3(kRedThreads), 0, st, A);
+void launch_lm_decide(const LmDecideArgs& A, bool stop, hipStream_t st) {
+  const dim3 grid(lm_decide_grid(A.n_points));
+  if (!stop) hipLaunchKernelGGL((ba_lm_decide_kernel<kRedThreads, false>), grid, dim3(kRedThreads), 0, st, A);
+  else hipLaunchKernelGGL((ba_lm_decide_kernel<kRedThreads, true>), grid, dim3(kRedThreads), 0, st, A);
+}
+
+void launch_lm_finish(int* status, hipStream_t st) {
+  hipLaunchKernelGGL(ba_lm_finish_kernel<64>, dim3(1), dim3(64), 0, st, status);
 }
 
 }  // namespace vo

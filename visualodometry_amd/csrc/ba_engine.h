@@ -20,6 +20,8 @@ int ba_gn_step(vo_ctx* ctx, double* S, double* b, double* dc, double* cost);
 int ba_run_lm(vo_ctx* ctx, int iters, const vo_ba_lm_options* opt, double* cost, double* lambda, double* trial,
               uint8_t* accepted, bool sync);
 int ba_lm_log(vo_ctx* ctx, int n, double* cost, double* lambda, double* trial, uint8_t* accepted);
+void ba_set_lm_stop(vo_ctx* ctx, const vo_ba_lm_stop* stop);
+void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason);
 void ba_set_robust(vo_ctx* ctx, double huber_delta);
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
 int ba_stats(vo_ctx* ctx, int64_t* out, int n);

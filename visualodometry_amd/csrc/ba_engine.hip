@@ -172,7 +172,8 @@ class BAEngine {
     pending_ = false;
     cur_ = 0;
     huber_ = 0.0;  // every problem starts with the plain cost
-    lm_iters_ = -1;  // and without an LM log
+    lm_iters_ = -1;  // without an LM log
+    lm_stop_ = vo_ba_lm_stop{};  // and with an LM loop that never stops early
     obs_uploaded_ = false;
     session_ = ++g_ba_sessions;
     return session_;
@@ -382,6 +383,11 @@ class BAEngine {
     lm_unread_ = true;
     lm_fail_ = 0;
     lm_timeout_ = false;
+    // termination (set_lm_stop): with a criterion set, the decide instantiation that tests it
+    const bool stop = lm_stop_.ftol > 0.0 || lm_stop_.xtol > 0.0 || lm_stop_.max_rejects > 0;
+    lm_stop_on_ = stop;
+    lm_trials_ = iters;
+    lm_reason_ = VO_BA_LM_RAN_ALL;
     LmDecideArgs D{};
     D.nseg = std::max(1, plan_.n_segments());
     D.n_points = plan_.n_points;
@@ -395,12 +401,18 @@ class BAEngine {
     D.points = d_points_.as<double>();
     D.snap = d_lm_snap_.as<double>();
     D.status = d_status_.as<int>();
+    D.ftol = lm_stop_.ftol;
+    D.xtol = lm_stop_.xtol;
+    D.max_rejects = lm_stop_.max_rejects;
+    D.n_dc = 6 * plan_.n_free;
+    D.dc = d_dc_.as<double>();
+    D.stop = D.accepted + std::max(1, iters);
     auto decide = [&](int k) {
       D.k = k;
       D.pose_cur = d_pose_[cur_ ^ 1].as<double>();
       D.pose_next = d_pose_[cur_].as<double>();
       ctx_->prof.begin(st, kKBaReduce);  // (no id of its own: vo_hip.h, kernel timing)
-      launch_lm_decide(D, st);
+      launch_lm_decide(D, stop, st);
       ctx_->prof.end(st);
       VO_HIP_CHECK(hipGetLastError());
     };
@@ -420,6 +432,12 @@ class BAEngine {
       decide(k);
     }
     lm_lambda_ = nullptr;
+    if (stop) {  // a stop word goes back to zero on the device: the next run needs no read in between
+      ctx_->prof.begin(st, kKBaReduce);
+      launch_lm_finish(d_status_.as<int>(), st);
+      ctx_->prof.end(st);
+      VO_HIP_CHECK(hipGetLastError());
+    }
     if (!sync) return VO_OK;
     return lm_read(iters, cost_out, lambda_out, trial_out, accepted_out, "vo_ba_run_lm");
   }
@@ -436,22 +454,18 @@ class BAEngine {
     const int N = lm_iters_;
     std::vector<double> log(3 * (size_t)N + 2);
     std::vector<int> acc(std::max(1, N));
-    int status = 0;
     VO_HIP_CHECK(hipMemcpyAsync(log.data(), d_lm_log_.ptr, log.size() * 8, hipMemcpyDeviceToHost, st));
     if (N)
       VO_HIP_CHECK(hipMemcpyAsync(acc.data(), d_lm_log_.as<double>() + log.size(), N * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (lm_unread_) VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipStreamSynchronize(st));
-    if (lm_unread_) {
-      lm_timeout_ = clear_failure(status);
-      lm_fail_ = status;
-      lm_unread_ = false;
-    }
+    lm_settle();
     const double *cost = log.data(), *lam = cost + N + 1, *trial = lam + N + 1;
-    const int f = lm_fail_ ? lm_fail_ - 1 : N;  // first iteration without a verdict
+    // first iteration without a verdict: the failed one, or the first behind a stop, whose cost and
+    // damping (the stopped state's) every later entry repeats
+    const int f = lm_fail_ ? lm_fail_ - 1 : lm_trials_;
+    const bool stopped = !lm_fail_ && lm_reason_ != VO_BA_LM_RAN_ALL;
     for (int k = 0; k <= n; ++k) {
-      if (cost_out) cost_out[k] = k <= f ? cost[k] : NAN;
-      if (lambda_out) lambda_out[k] = k <= f ? lam[k] : NAN;
+      if (cost_out) cost_out[k] = k <= f ? cost[k] : stopped ? cost[f] : NAN;
+      if (lambda_out) lambda_out[k] = k <= f ? lam[k] : stopped ? lam[f] : NAN;
     }
     for (int k = 0; k < n; ++k) {
       if (trial_out) trial_out[k] = k < f ? trial[k] : NAN;
@@ -466,6 +480,52 @@ class BAEngine {
     return VO_OK;
   }
 
+  // Synchronises; on the first read after an LM run also takes the status word (a failure is
+  // cleared as after any run) and, from a run with a termination criterion, the two control words
+  // behind the log.
+  void lm_settle() {
+    hipStream_t st = ctx_->stream;
+    int status = 0, words[2] = {0, 0};
+    if (lm_unread_) {
+      VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+      if (lm_stop_on_)
+        VO_HIP_CHECK(hipMemcpyAsync(words, d_lm_log_.as<char>() + lm_log_bytes(lm_iters_) - sizeof(words),
+                                    sizeof(words), hipMemcpyDeviceToHost, st));
+    }
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    if (!lm_unread_) return;
+    lm_timeout_ = clear_failure(status);
+    lm_fail_ = status;
+    lm_unread_ = false;
+    if (lm_fail_) {
+      lm_trials_ = lm_fail_ - 1;
+      lm_reason_ = VO_BA_LM_FAILED;
+    } else if (words[1] != VO_BA_LM_RAN_ALL) {
+      lm_trials_ = words[0];
+      lm_reason_ = words[1];
+    }
+  }
+
+  // vo_ba_lm_stop_info: how the session's last LM run ended.
+  void lm_stop_info(int32_t* trials_out, int32_t* reason_out) {
+    VO_REQUIRE(lm_iters_ >= 0 && lm_session_ == session_, VO_ERR_STATE, "vo_ba_lm_stop_info: no vo_ba_run_lm on this session");
+    lm_settle();
+    if (trials_out) *trials_out = lm_trials_;
+    if (reason_out) *reason_out = lm_reason_;
+  }
+
+  // The termination criteria of the later LM runs (vo_hip.h vo_ba_set_lm_stop); null: never stop.
+  void set_lm_stop(const vo_ba_lm_stop* s) {
+    VO_REQUIRE(have_problem_, VO_ERR_STATE, "vo_ba_set_lm_stop before vo_ba_setup");
+    const vo_ba_lm_stop v = s ? *s : vo_ba_lm_stop{};
+    VO_REQUIRE(std::isfinite(v.ftol) && std::isfinite(v.xtol), VO_ERR_ARG, "vo_ba_set_lm_stop: non-finite tolerance");
+    VO_REQUIRE(v.ftol >= 0.0 && v.ftol < 1.0, VO_ERR_ARG, "vo_ba_set_lm_stop: ftol must be in [0, 1)");
+    VO_REQUIRE(v.xtol >= 0.0, VO_ERR_ARG, "vo_ba_set_lm_stop: xtol < 0");
+    VO_REQUIRE(v.max_rejects >= 0, VO_ERR_ARG, "vo_ba_set_lm_stop: max_rejects < 0");
+    VO_REQUIRE(v.reserved == 0, VO_ERR_ARG, "vo_ba_set_lm_stop: reserved must be 0");
+    lm_stop_ = v;
+  }
+
   // After a failed fused launch (any non-zero status; kBandStatusTimeout: the solver gave up
   // waiting for its reducers) the reducer counter is re-zeroed -- the stream is synchronised,
   // so every late reducer has counted itself by now -- and the timeout flag is stripped from
@@ -475,7 +535,8 @@ class BAEngine {
     hipStream_t st = ctx_->stream;
     if (status && fuse_ok_) VO_HIP_CHECK(hipMemsetAsync(d_colcnt_.ptr, 0, colcnt_bytes_, st));
     const bool timed_out = status & kBandStatusTimeout;
-    status &= ~kBandStatusTimeout;
+    // (an LM stop word is only ever seen here with a later launch's timeout flag on it: ba_lm_finish)
+    status &= ~(kBandStatusTimeout | kLmStatusStopped);
     if (status) {
       VO_HIP_CHECK(hipMemsetAsync(d_status_.ptr, 0, sizeof(int), st));
       VO_HIP_CHECK(hipStreamSynchronize(st));
@@ -553,8 +614,8 @@ class BAEngine {
   }
 
   // The log of an LM run of n iterations: cost (n + 1), lambda (n + 1), trial (n) doubles, then
-  // the n decisions (ints).
-  static size_t lm_log_bytes(int n) { return (3 * (size_t)n + 2) * 8 + std::max(1, n) * sizeof(int); }
+  // the n decisions (ints) and the two control words of a stop (trials, reason; LmDecideArgs::stop).
+  static size_t lm_log_bytes(int n) { return (3 * (size_t)n + 2) * 8 + (std::max(1, n) + 2) * sizeof(int); }
 
   // vo_ba_run_lm's options with the defaults filled in (vo_hip.h); VO_ERR_ARG for a bad field.
   vo_ba_lm_options lm_options(const vo_ba_lm_options* opt) const {
@@ -1111,6 +1172,11 @@ class BAEngine {
   int lm_iters_ = -1, lm_fail_ = 0;
   uint64_t lm_session_ = 0;
   bool lm_unread_ = false, lm_timeout_ = false;
+  // termination: the session's criteria (all zero: never stop), whether the last run tested any,
+  // and how it ended (settled at its first read)
+  vo_ba_lm_stop lm_stop_{};
+  bool lm_stop_on_ = false;
+  int lm_trials_ = 0, lm_reason_ = VO_BA_LM_RAN_ALL;
   // residuals(): the problem-order observation arrays (uploaded on a session's first call) and
   // its output [err2 | depth]
   bool obs_uploaded_ = false;
@@ -1142,6 +1208,8 @@ int ba_run_lm(vo_ctx* ctx, int iters, const vo_ba_lm_options* opt, double* cost,
 int ba_lm_log(vo_ctx* ctx, int n, double* cost, double* lambda, double* trial, uint8_t* accepted) {
   return ba_engine(ctx)->lm_read(n, cost, lambda, trial, accepted, "vo_ba_lm_log");
 }
+void ba_set_lm_stop(vo_ctx* ctx, const vo_ba_lm_stop* stop) { ba_engine(ctx)->set_lm_stop(stop); }
+void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason) { ba_engine(ctx)->lm_stop_info(trials, reason); }
 void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta); }
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }
 int ba_stats(vo_ctx* ctx, int64_t* out, int n) { return ba_engine(ctx)->stats(out, n); }

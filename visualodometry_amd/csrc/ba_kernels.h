@@ -116,6 +116,16 @@ void launch_obs_residual(const ObsResidualArgs& A, hipStream_t st);
 // (t < c) the points become the new snapshot, rejected they are restored from it and pose_next
 // (the trial poses) is overwritten with pose_cur; workgroup 0 appends entry k + 1 to the log.
 // k < 0: the initial cost, lambda0 and the first snapshot.  Nothing is written once *status is set.
+//
+// Termination (vo_ba_set_lm_stop; the kStop instantiation, launched only when a criterion is set):
+// workgroup 0 also tests the decision against ftol / xtol / max_rejects (vo_hip.h) and on a stop
+// writes stop[0] = k + 1, stop[1] = the reason and the status word kLmStatusStopped | (k + 1), so
+// every later launch of the run goes quiet through its own status test.  A workgroup of this very
+// launch that starts late may already see that word: carrying the launch's own tag it counts as
+// zero there, so the workgroup still makes its copies.  ba_lm_finish, enqueued behind the last
+// trial, zeroes a status word that is exactly a stop word (no failure tag, no timeout flag).
+constexpr int kLmStatusStopped = 1 << 29;  // beside kBandStatusTimeout (ba_band.h); low bits: trials
+enum { kLmRanAll = 0, kLmFtol = 1, kLmXtol = 2, kLmRejects = 3 };  // vo_hip.h VO_BA_LM_*
 struct LmDecideArgs {
   int k, nseg, n_points, n_poses;
   double lambda0, up, down, lambda_min, lambda_max;
@@ -128,10 +138,17 @@ struct LmDecideArgs {
   double* snap;        // the accepted state's landmarks
   const double* pose_cur;  // the accepted poses
   double* pose_next;       // the trial poses
-  const int* status;
+  int* status;
+  // read by the kStop instantiation only
+  double ftol, xtol;   // 0: not tested
+  int max_rejects;     // 0: not tested
+  int n_dc;            // 6 per free camera
+  const double* dc;    // the pose update K3 wrote for trial k
+  int* stop;           // control words behind the log: [trials, reason]
 };
 int lm_decide_grid(int n_points);
-void launch_lm_decide(const LmDecideArgs& A, hipStream_t st);
+void launch_lm_decide(const LmDecideArgs& A, bool stop, hipStream_t st);
+void launch_lm_finish(int* status, hipStream_t st);
 
 // Runs of consecutive chunk images copied from the previous plan's device images (ba.hip
 // ba_img_copy_kernel); they travel in the arguments.

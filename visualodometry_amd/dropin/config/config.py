@@ -51,6 +51,10 @@ class VOConfig:
     ba_lambda: float = 1.0  # Levenberg damping: fixed (ba_lm off), or the starting value of the LM schedule
     ba_huber: float = 0.0  # Huber delta of the BA cost in pixels; 0: plain sum of squares
     ba_lm: bool = False  # Levenberg-Marquardt step control on the device (accept / reject, adaptive damping)
+    # termination of the LM loop, decided on the device (with ba_lm only); 0: not tested
+    ba_lm_ftol: float = 0.0  # stop once an accepted step lowers the cost by at most this fraction
+    ba_lm_xtol: float = 0.0  # stop once an accepted step's largest pose-update entry is at most this
+    ba_lm_max_rejects: int = 0  # stop after this many rejected steps in a row
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)
