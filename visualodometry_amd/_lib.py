@@ -148,6 +148,16 @@ SIGNATURES = {
     "vo_ba_testing_plan_slide": (_I, [C.c_void_p, C.c_void_p, _I, _I, C.POINTER(C.c_uint64), _PI64]),
 }
 
+# the chained GN loop's test and tool entry points (include/vo_hip_testing_chain.h, a header of
+# its own: tests/test_abi.py pins the list of vo_hip_testing.h and SIGNATURES to the two above)
+CHAIN_TEST_HEADER = HEADER.with_name("vo_hip_testing_chain.h")
+CHAIN_SIGNATURES = {
+    "vo_ba_testing_no_chain": (_I, [_P, _I]),
+    "vo_ba_testing_last_run": (_I, [_P, _PI32, _PI32]),
+    "vo_ba_testing_chain_poll": (_I, [_P, _I]),
+    "vo_ba_testing_chain_stamps": (_I, [_P, _I, C.POINTER(C.c_uint64), _I]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -164,7 +174,7 @@ def load() -> C.CDLL:
                 )
             lib = C.CDLL(str(LIB_PATH))
             tuning = bool(os.environ.get("VO_LIB_PATH"))
-            for name, (res, args) in SIGNATURES.items():
+            for name, (res, args) in {**SIGNATURES, **CHAIN_SIGNATURES}.items():
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -338,6 +348,38 @@ def ba_testing_k1(ctx: "Context", variant: int = 0) -> None:
     """Test switch: the K1 variant of the context's later setups (0 default, -1 four-wave K1,
     n = 1..6 one-wave K1 with n chunks per segment); see vo_ba_testing_k1."""
     check(ctx.lib.vo_ba_testing_k1(ctx.handle, int(variant)), "vo_ba_testing_k1")
+
+
+def ba_testing_no_chain(ctx: "Context", on: bool = True) -> None:
+    """Test switch: the context's later runs keep the split sequence (a K1 launch and a solve
+    launch per iteration) instead of chaining the next K1 into the solve launch; see
+    vo_ba_testing_no_chain."""
+    check(ctx.lib.vo_ba_testing_no_chain(ctx.handle, int(bool(on))), "vo_ba_testing_no_chain")
+
+
+def ba_testing_last_run(ctx: "Context") -> tuple:
+    """(chained, launches) of the context's last BA run; see vo_ba_testing_last_run."""
+    ch, n = C.c_int32(0), C.c_int32(0)
+    check(ctx.lib.vo_ba_testing_last_run(ctx.handle, C.byref(ch), C.byref(n)), "vo_ba_testing_last_run")
+    return bool(ch.value), n.value
+
+
+def ba_testing_chain_poll(ctx: "Context", replicas: int = 0) -> None:
+    """Tool switch: publish-word replicas the chained K1 workgroups poll (0 default, 1 or 8)."""
+    check(ctx.lib.vo_ba_testing_chain_poll(ctx.handle, int(replicas)), "vo_ba_testing_chain_poll")
+
+
+def ba_testing_chain_stamps(ctx: "Context", on: bool = True, n: int = 0):
+    """Tool entry (stamped builds): let stamped runs chain, and read the last chained launch's
+    realtime stamps (uint64 array, empty in a product build); see vo_ba_testing_chain_stamps."""
+    import numpy as np
+
+    out = np.zeros(max(n, 1), dtype=np.uint64)
+    k = ctx.lib.vo_ba_testing_chain_stamps(ctx.handle, int(bool(on)), out.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                           int(n))
+    if k < 0:
+        check(k, "vo_ba_testing_chain_stamps")
+    return out[:k]
 
 
 def pnp_testing_group(ctx: "Context", mode: int = 0) -> None:

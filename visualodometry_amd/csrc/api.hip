@@ -11,6 +11,7 @@
 #include "ba_plan.h"
 #include "vo_ctx.h"
 #include "../../include/vo_hip_testing.h"
+#include "../../include/vo_hip_testing_chain.h"
 
 namespace vo {
 
@@ -1006,6 +1007,41 @@ int vo_ba_testing_no_split(vo_ctx* ctx, int on) {
     VO_REQUIRE(ctx != nullptr, VO_ERR_ARG, "vo_ba_testing_no_split: null context");
     ctx->ba_no_split = on != 0;
   });
+}
+
+int vo_ba_testing_no_chain(vo_ctx* ctx, int on) {
+  return guarded([&] {
+    VO_REQUIRE(ctx != nullptr, VO_ERR_ARG, "vo_ba_testing_no_chain: null context");
+    ctx->ba_no_chain = on != 0;
+  });
+}
+
+int vo_ba_testing_last_run(vo_ctx* ctx, int* chained, int* launches) {
+  return guarded([&] {
+    VO_REQUIRE(ctx != nullptr, VO_ERR_ARG, "vo_ba_testing_last_run: null context");
+    vo::bind(ctx);
+    vo::ba_last_run(ctx, chained, launches);
+  });
+}
+
+int vo_ba_testing_chain_poll(vo_ctx* ctx, int replicas) {
+  return guarded([&] {
+    VO_REQUIRE(ctx != nullptr, VO_ERR_ARG, "vo_ba_testing_chain_poll: null context");
+    VO_REQUIRE(replicas == 0 || replicas == 1 || replicas == 8, VO_ERR_ARG,
+               "vo_ba_testing_chain_poll: %d replicas (0, 1 or 8)", replicas);
+    ctx->ba_chain_poll = replicas;
+  });
+}
+
+int vo_ba_testing_chain_stamps(vo_ctx* ctx, int on, uint64_t* out, int n) {
+  int k = 0;
+  int g = guarded([&] {
+    VO_REQUIRE(ctx != nullptr, VO_ERR_ARG, "vo_ba_testing_chain_stamps: null context");
+    vo::bind(ctx);
+    ctx->ba_chain_stamps = on != 0;
+    if (out && n > 0) k = vo::ba_chain_stamps(ctx, out, n);
+  });
+  return g != VO_OK ? g : k;
 }
 
 int vo_ba_testing_k1(vo_ctx* ctx, int variant) {

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <vector>
 
+#include "ba_kernels.h"
 #include "ba_reduce.h"
 
 namespace vo {
@@ -76,7 +77,22 @@ struct BandArgs {
   const int* red_col;    // per reduction item (profile block): its column's counter
   const int* col_need;   // per counter: the items that store into that column (F + 1)
   ReduceArgs red;
+  // Chained launch (k1_nseg > 0; full layout, fused K2): the last k1_nseg workgroups of the launch
+  // are the NEXT iteration's K1 segments (six chunks each, `lin` its arguments: pose_old is this
+  // solve's pose_cur, pose_new its pose_next).  Each does its solve-independent loads, then waits
+  // at its pose gate (ba_lin_wave.h LinGate) for the solver's publish word: pub[kBandPubStride * r],
+  // r = workgroup index & pub_mask (pub_mask + 1 = 1 or 8 replicas, each on a line of its own),
+  // which the solver sets to seq << 1 | verdict once pose_next and dc are out (write-through).
+  int k1_nseg = 0;
+  int pub_mask = 0;
+  unsigned* pub = nullptr;
+  unsigned long long* k1_stamps = nullptr;  // diagnostic build: [published, launch start | 4 per K1 workgroup]
+  LinArgs lin;
 };
+constexpr int kBandPubStride = 32;   // words between the publish word's replicas (128-byte lines)
+constexpr int kBandPubReplicas = 8;
+constexpr int kBandChainChunks = 6;  // chunks per segment of the K1 a chained launch carries
+size_t band_chain_lds();             // dynamic LDS a chained launch's K1 workgroups need
 // Split mode's exchange area at the front of BandArgs::fac (doubles): the bottom's merge sources
 // (n_merge), the top's separator records (42 doubles a row: L_kk's six rows, 1/diag), the
 // separator's z (6 s), two failure words, and three hand-off flags 128 bytes apart (each set to

@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <climits>
 
+#include "ba_lin_wave.h"
 #include "ba_math.h"
 #include "vo_common.h"
 
@@ -384,7 +385,11 @@ __device__ __forceinline__ bool xch_flag_wait(const double* fac, long flag, unsi
 // separator's z cross over through global memory once each: see the split hand-offs below).
 // kLm: the fused launch of a step-control iteration (its reducers read the damping from the
 // device; full mode only, the one that fuses); the solver's code does not depend on it.
-template <int kMode, bool kLm = false>
+// kNext: the chained launch (BandArgs::k1_nseg; full mode with fused K2 only).  1: the launch's
+// last k1_nseg workgroups run the next iteration's K1 (kBacksub | kAccum, six chunks per
+// segment) behind a pose gate, and the solver's tail publishes to them; 2: the same with the
+// Huber K1.  0: the launches as before, their code untouched.
+template <int kMode, bool kLm = false, int kNext = 0>
 __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
   constexpr bool kFull = kMode != 0, kSplit = kMode == 2;
   constexpr int NT = kSplit ? kBandThreads / 2 : kBandThreads;  // threads of this workgroup
@@ -397,6 +402,33 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
   // wave (so role and side) is wave-uniform: readfirstlane lets the compiler branch on SGPRs
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   // split mode: workgroup s is side s, its four waves the side's four roles
+  if constexpr (kNext != 0) {
+    static_assert(kMode == 1 && !kLm, "chained: the full layout's GN launch");
+    // the next iteration's K1 segment k1 (uniform branch): six waves, one per chunk, on the
+    // workgroup's dynamic LDS (six images, the arrival word, the gate's verdict)
+    const int k1 = (int)blockIdx.x - ((int)gridDim.x - A.k1_nseg);
+    if (k1 >= 0) {
+      if (wave >= kBandChainChunks) return;
+      LinWave* Sw = reinterpret_cast<LinWave*>(dyn);
+      int* words = reinterpret_cast<int*>(Sw + kBandChainChunks);
+      LinGate G;
+      G.pub = A.pub + kBandPubStride * ((int)blockIdx.x & A.pub_mask);
+      G.want = A.seq << 1;
+      G.status = A.status;
+      G.iter_tag = A.iter_tag;
+      G.timeout_flag = kBandStatusTimeout;
+      G.s_gate = (lin_lds_int*)(words + 1);
+#if VO_BA_STAMPS
+      if (A.k1_stamps) {
+        G.stamps = A.k1_stamps + 2 + 4 * k1;
+        if (tid == 0) G.stamps[0] = __builtin_amdgcn_s_memrealtime();
+      }
+#endif
+      constexpr int kMode1 = kBacksub | kAccum | (kNext == 2 ? kRobust : 0);
+      lin_wave_body<kMode1, false, kBandChainChunks, true>(A.lin, Sw, words, k1, G);
+      return;
+    }
+  }
   if (A.nred > 0 && blockIdx.x > 0) {  // fused K2: a reducer workgroup (uniform branch)
     band_reduce_wg<kLm>(A, blockIdx.x - 1, dyn);
     return;
@@ -1309,12 +1341,36 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
     }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __syncthreads();
+  if constexpr (kNext != 0) {
+    // Chained launch: the same 16-byte pieces go out write-through (sc1), every storing wave
+    // drains them, and behind the workgroup barrier one lane per replica stores the publish word
+    // -- this launch's sequence number and the verdict (a failed or timed-out solve, or an earlier
+    // failure: the K1 workgroups then apply nothing).  They poll it relaxed and read pose_next and
+    // dc by sc1 loads only (MI355X_MICROARCH.md, hand-off table row 1).
+    for (int e = tid; e < 6 * A.n_poses; e += NT)
+      slab_store(reinterpret_cast<double2*>(A.pose_next) + e, reinterpret_cast<const double2*>(pose_l)[e]);
+    for (int e = tid; e < 3 * (A.n_poses - A.n_fixed); e += NT)
+      slab_store(reinterpret_cast<double2*>(A.dc) + e,
+                 failed2 ? make_double2(0.0, 0.0) : reinterpret_cast<const double2*>(zs)[e]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid <= A.pub_mask)
+      __hip_atomic_store((gu32*)(A.pub + kBandPubStride * tid), A.seq << 1 | (failed2 ? 1u : 0u), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+#if VO_BA_STAMPS
+    if (A.k1_stamps && tid == 0) {
+      A.k1_stamps[0] = __builtin_amdgcn_s_memrealtime();
+      A.k1_stamps[1] = sst ? sst[0] : 0;
+    }
+#endif
+  } else {
   for (int e = tid; e < 6 * A.n_poses; e += NT)
     if (mine(e / 6 - A.n_fixed))
       reinterpret_cast<double2*>(A.pose_next)[e] = reinterpret_cast<const double2*>(pose_l)[e];
   for (int e = tid; e < 3 * (A.n_poses - A.n_fixed); e += NT)
     if (mine(e / 3))
       reinterpret_cast<double2*>(A.dc)[e] = failed2 ? make_double2(0.0, 0.0) : reinterpret_cast<const double2*>(zs)[e];
+  }
   // A timeout is recorded whatever the earlier status (the counter then holds this launch's
   // reducers: the host re-zeroes it when it reads the flag); a failed factorisation only when
   // no earlier step failed (the status names the first failed iteration).
@@ -1339,6 +1395,11 @@ __global__ __launch_bounds__(kBandThreads) void ba_band_kernel(BandArgs A) {
 static size_t band_launch_lds(const BandLds& L, bool fused) {
   return fused ? std::max(L.bytes, (size_t)kBandRedItems * kRedScr * sizeof(double)) : L.bytes;
 }
+// A chained launch's K1 workgroups: six LDS images, the arrival word and the gate's verdict.  At
+// ~153 KB a K1 workgroup has its CU to itself, as the stand-alone six-chunk K1's has.
+static_assert(kWaveMaxChunks >= kBandChainChunks && kBandChainChunks * sizeof(LinWave) + 16 <= kBandLdsMax,
+              "the chained K1's images fit the launch's dynamic LDS");
+size_t band_chain_lds() { return kBandChainChunks * sizeof(LinWave) + 16; }
 
 // The kernels' dynamic-LDS limit (process-wide), raised only when a window needs more than
 // any before it: a hipFuncSetAttribute costs host time on every keyframe otherwise.
@@ -1352,6 +1413,15 @@ void band_set_attributes(const BandLds& L) {
   for (const void* f : fs) VO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   while (cur < lds && !set.compare_exchange_weak(cur, lds, std::memory_order_relaxed)) {
   }
+  // the chained instantiations: always at least their K1 workgroups' images
+  static std::atomic<int> set_chain{-1};
+  const int ldc = (int)std::max((size_t)lds, band_chain_lds());
+  cur = set_chain.load(std::memory_order_relaxed);
+  if (ldc <= cur) return;
+  const void* fc[2] = {(const void*)ba_band_kernel<1, false, 1>, (const void*)ba_band_kernel<1, false, 2>};
+  for (const void* f : fc) VO_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ldc));
+  while (cur < ldc && !set_chain.compare_exchange_weak(cur, ldc, std::memory_order_relaxed)) {
+  }
 }
 
 void launch_band_solve(const BandArgs& A, const BandLds& L, hipStream_t st) {
@@ -1359,6 +1429,15 @@ void launch_band_solve(const BandArgs& A, const BandLds& L, hipStream_t st) {
   // fewer than the solver waits for: vo_ba_testing_drop_reducers)
   const dim3 grid(1 + std::max(A.nred - std::max(A.red_drop, 0), 0));
   const size_t lds = band_launch_lds(L, A.nred > 0);
+  if (A.k1_nseg > 0) {  // chained (the engine checked: full layout, fused K2, no step control)
+    const dim3 gc(grid.x + A.k1_nseg);
+    const size_t ldc = std::max(lds, band_chain_lds());
+    if (A.lin.huber > 0.0)
+      hipLaunchKernelGGL((ba_band_kernel<1, false, 2>), gc, dim3(kBandThreads), ldc, st, A);
+    else
+      hipLaunchKernelGGL((ba_band_kernel<1, false, 1>), gc, dim3(kBandThreads), ldc, st, A);
+    return;
+  }
   if (L.split)  // one workgroup of four waves per side (K2 never fused: BAEngine::fused)
     hipLaunchKernelGGL((ba_band_kernel<2>), dim3(2), dim3(kBandThreads / 2), lds, st, A);
   else if (L.full && A.nred > 0 && A.red.lm_lambda)  // step control: the reducers' damping is on the device

@@ -26,5 +26,7 @@ void ba_set_robust(vo_ctx* ctx, double huber_delta);
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
 int ba_stats(vo_ctx* ctx, int64_t* out, int n);
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n);
+int ba_chain_stamps(vo_ctx* ctx, uint64_t* out, int n);
+void ba_last_run(vo_ctx* ctx, int* chained, int* launches);
 
 }  // namespace vo

@@ -17,6 +17,12 @@
 #include "ba_plan.h"
 #include "vo_ctx.h"
 
+#ifndef VO_BA_CHAIN
+#define VO_BA_CHAIN 1  // tuning build: 0 never chains the next K1 into the solve launch
+#endif
+#ifndef VO_BA_CHAIN_POLL
+#define VO_BA_CHAIN_POLL 8  // replicas of the chained launch's publish word (1 or 8)
+#endif
 #ifndef VO_BA_FUSE
 #define VO_BA_FUSE 1  // tuning build: 0 launches K2 on its own
 #endif
@@ -341,7 +347,14 @@ class BAEngine {
     VO_REQUIRE(iters >= 0, VO_ERR_ARG, "vo_ba_run: iters < 0");
     hipStream_t st = ctx_->stream;
     d_cost_.reserve((iters + 1) * 8ull);
-    for (int it = 0; it < iters; ++it) iteration(d_cost_.as<double>() + it, it + 1);
+    // Chained (chain_ok): a stand-alone K1, then iters - 1 solve launches that each carry the next
+    // iteration's K1 behind its pose gate, then one plain fused launch (the last iteration has no
+    // successor; finalize keeps its back-substitute-only K1).
+    const bool chain = iters >= 2 && chain_ok();
+    last_chained_ = chain;
+    const int launches0 = launches_;
+    for (int it = 0; it < iters; ++it) iteration(d_cost_.as<double>() + it, it + 1, chain && it > 0, chain && it + 1 < iters);
+    last_launches_ = launches_ - launches0;  // K1 and solve launches of the iterations
     if (!sync) return VO_OK;
     finalize_cost(d_cost_.as<double>() + iters);
     std::vector<double> costs(iters + 1);
@@ -594,6 +607,21 @@ class BAEngine {
     return VO_OK;
   }
 
+  void last_run(int* chained, int* launches) const {
+    if (chained) *chained = last_chained_ ? 1 : 0;
+    if (launches) *launches = last_launches_;
+  }
+
+  // Diagnostic build: the last chained launch's realtime stamps (100 MHz ticks), [published,
+  // launch start | start, prefix done, gate passed, end per K1 workgroup]; returns the count.
+  int read_chain_stamps(uint64_t* out, int n) {
+    if (!stamps_on_ || !d_stamps_k1_.ptr || !last_chained_) return 0;
+    const int k = std::min(n, 2 + 4 * plan_.n_segments());
+    VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
+    VO_HIP_CHECK(hipMemcpy(out, d_stamps_k1_.ptr, (size_t)k * 8, hipMemcpyDeviceToHost));
+    return k;
+  }
+
   int stats(int64_t* out, int n) const {
     const BAPlan& P = plan_;
     int64_t v[12 + kSetupSections] = {P.n_chunks(), P.n_segments(), P.n_slab_slots(), (int64_t)P.slot_i.size(),
@@ -844,6 +872,10 @@ class BAEngine {
     colcnt_bytes_ = band_col_count_bytes(plan_.n_free);
     d_colcnt_.reserve(colcnt_bytes_);
     VO_HIP_CHECK(hipMemsetAsync(d_colcnt_.ptr, 0, colcnt_bytes_, st));
+    // the chained launches' publish word, its replicas on lines of their own (a stale word is
+    // another launch's sequence number: never a match)
+    d_pub_.reserve(kBandPubReplicas * kBandPubStride * sizeof(unsigned));
+    VO_HIP_CHECK(hipMemsetAsync(d_pub_.ptr, 0, kBandPubReplicas * kBandPubStride * sizeof(unsigned), st));
   }
 
   // Planner target of one K1 round: as many segments as resident workgroups (three per CU,
@@ -924,6 +956,7 @@ class BAEngine {
     VO_REQUIRE(!wave || ((int64_t)nseg * nw == plan_.n_chunks() && nw >= 1 && nw <= kWaveMaxChunks), VO_ERR_STATE,
                "K1: segments of seg_chunks chunks expected");
     A.nseg = nseg;
+    ++launches_;
     ctx_->prof.begin(ctx_->stream, kKBaLin);
     if (stamps_on_) {  // one row per chunk (one-wave K1) or segment (four-wave K1)
       d_stamps_.reserve((size_t)plan_.n_chunks() * kPhCount * 8);
@@ -971,7 +1004,8 @@ class BAEngine {
       ctx_->comm->allreduce(d_sys_.as<double>(), sys_len_, false, ctx_->stream);
   }
 
-  void launch_solve(const SolveArgs& A) {
+  void launch_solve(const SolveArgs& A, bool chain_next = false) {
+    ++launches_;
     if (band_on_) {
       BandArgs B;
       B.F = A.F;
@@ -990,7 +1024,11 @@ class BAEngine {
       B.sys = A.sys;
       B.zero = d_zero_.as<double>();
       B.fac = band_lds_.full && !band_lds_.split ? nullptr : d_fac_.as<double>();
-      B.seq = ++band_seq_ == 0 ? ++band_seq_ : band_seq_;  // split hand-off flags: new every launch
+      // split hand-off flags and the chained launch's publish word (seq << 1 | verdict): new every
+      // launch, the low 31 bits never zero
+      while ((++band_seq_ & 0x7fffffffu) == 0) {
+      }
+      B.seq = band_seq_;
       B.cost_out = A.cost_out;
       B.dc = A.dc;
       B.pose_cur = A.pose_cur;
@@ -1007,13 +1045,26 @@ class BAEngine {
         d_stamps3_.reserve((8 * kBandStamps + 8 + 4 * (B.nred + 1)) * 8);
         B.stamps = d_stamps3_.as<unsigned long long>();
       }
+      if (chain_next) {
+        // the next iteration's K1 (iteration() flips cur_ behind this launch): its pending step's
+        // linearisation point is this solve's input, its own the poses this solve writes
+        B.lin = lin_args();
+        std::swap(B.lin.pose_old, B.lin.pose_new);
+        B.lin.nseg = B.k1_nseg = plan_.n_segments();
+        B.pub_mask = (ctx_->ba_chain_poll ? ctx_->ba_chain_poll : kChainPollReplicas) - 1;
+        B.pub = d_pub_.as<unsigned>();
+        if (stamps_on_) {  // [published, launch start | start, prefix done, gate passed, end per K1 workgroup]
+          d_stamps_k1_.reserve((2 + 4 * (size_t)B.k1_nseg) * 8);
+          B.k1_stamps = d_stamps_k1_.as<unsigned long long>();
+        }
+      }
       launch_band_solve(B, band_lds_, ctx_->stream);
       return;
     }
     launch_profile_solve(A, solve_lds_, solve_lds_size_, ctx_->stream);
   }
 
-  void enqueue_solve(int iter_tag, double* cost_slot = nullptr) {
+  void enqueue_solve(int iter_tag, double* cost_slot = nullptr, bool chain_next = false) {
     const BAPlan& P = plan_;
     SolveArgs A;
     A.F = P.n_free;
@@ -1043,17 +1094,32 @@ class BAEngine {
       A.stamps = d_stamps3_.as<unsigned long long>();
     }
     ctx_->prof.begin(ctx_->stream, kKBaSolve);
-    launch_solve(A);
+    launch_solve(A, chain_next);
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
   }
 
-  void iteration(double* d_cost_slot, int iter_tag) {
-    enqueue_lin(pending_ ? (kBacksub | kAccum) : kAccum);
+  // lin_done: this iteration's K1 rode in the previous solve launch; chain_next: this solve
+  // launch carries the next iteration's K1 (run()).
+  void iteration(double* d_cost_slot, int iter_tag, bool lin_done = false, bool chain_next = false) {
+    if (!lin_done) enqueue_lin(pending_ ? (kBacksub | kAccum) : kAccum);
     enqueue_reduce();
-    enqueue_solve(iter_tag, d_cost_slot);  // K3 also stores the cost (no extra copy node)
+    enqueue_solve(iter_tag, d_cost_slot, chain_next);  // K3 also stores the cost (no extra copy node)
     cur_ ^= 1;
     pending_ = true;
+  }
+
+  // Whether a run's solve launches may carry the next iteration's K1: the
+  // fused K2 + K3 launch of the full layout, a wave plan of six chunks per segment, every K1
+  // workgroup resident beside the solver with a CU left for the reducers to pass through
+  // (nseg + 2 <= CUs: the launch then completes under any dispatch order), one rank, and neither
+  // kernel profiling nor stamps (a stamped build chains only when a tool asks for it).
+  bool chain_ok() const {
+    const int nseg = plan_.n_segments();
+    return VO_BA_CHAIN && !ctx_->ba_no_chain && band_on_ && fused() && band_lds_.full && !band_lds_.split &&
+           plan_is_wave(plan_.seg_obs) && plan_.seg_chunks == kBandChainChunks && nseg > 0 &&
+           (int64_t)nseg * kBandChainChunks == plan_.n_chunks() && nseg + 2 <= ctx_->num_cus && !lm_lambda_ &&
+           !ctx_->prof.on && (!stamps_on_ || ctx_->ba_chain_stamps) && !sharded();
   }
 
   // Applies the pending point update (if any) and writes the cost at the
@@ -1114,6 +1180,12 @@ class BAEngine {
   DevBuf d_misc_;  // [status | zero block (512 B)]
   DevView d_status_, d_zero_;
   DevBuf d_colcnt_;  // the fused launch's column readiness counters (band_col_count_bytes)
+  DevBuf d_pub_;     // the chained launches' publish word (kBandPubReplicas lines)
+  DevBuf d_stamps_k1_;  // diagnostic build: the chained K1 workgroups' realtime stamps
+  // replicas of the publish word the K1 workgroups poll (one word against eight)
+  static constexpr int kChainPollReplicas = VO_BA_CHAIN_POLL;
+  bool last_chained_ = false;  // the last run(): chained, and the solve launches it made
+  int last_launches_ = 0, launches_ = 0;
   size_t colcnt_bytes_ = 0;
   DevView d_red_col_, d_col_need_;
   std::vector<int32_t> red_col_, col_need_;
@@ -1214,6 +1286,8 @@ void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }
 int ba_stats(vo_ctx* ctx, int64_t* out, int n) { return ba_engine(ctx)->stats(out, n); }
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_stamps(out, n); }
+int ba_chain_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_chain_stamps(out, n); }
+void ba_last_run(vo_ctx* ctx, int* chained, int* launches) { ba_engine(ctx)->last_run(chained, launches); }
 
 }  // namespace vo
 

@@ -146,6 +146,9 @@ struct vo_ctx {
   bool ba_no_split = false;      // test switch (vo_ba_testing_no_split): no split band layout at setup
   int pnp_group = 0;      // test switch (vo_pnp_testing_group): 0 auto, 1 lane groups, -1 one lane per hypothesis
   int pnp_split = 0;      // test/tool switch (vo_pnp_testing_split): 0 auto, -1 never, n > 0 first n hypotheses
+  bool ba_no_chain = false;      // test switch (vo_ba_testing_no_chain): no K1 chained into the solve launch
+  int ba_chain_poll = 0;         // tool switch (vo_ba_testing_chain_poll): publish word replicas, 0 the default
+  bool ba_chain_stamps = false;  // tool switch (vo_ba_testing_chain_stamps): stamped builds chain and stamp the gate
   int ba_k1_variant = 0;  // test switch (vo_ba_testing_k1): -1 four-wave K1, n >= 1 one-wave K1 of n chunks per segment
   vo_ctx();
   ~vo_ctx();
