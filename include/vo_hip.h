@@ -301,6 +301,34 @@ int vo_ba_set_robust(vo_ctx* ctx, uint64_t session, double huber_delta);
  * depth z, at the device-resident state (after any pending landmark update).  With a
  * communicator: the rank's own observations. */
 int vo_ba_residuals(vo_ctx* ctx, uint64_t session, double* err2_out, double* depth_out);
+/* Covariance read-out at the device-resident state (after any pending landmark update), for UNIT
+ * pixel variance: the caller scales every value by sigma^2, its estimate of the measurement
+ * variance in pixels^2 (e.g. final cost / degrees of freedom).
+ * H = J^T J of the session's problem in the solver's own parametrisation (the left se(3) twist
+ * (rho, phi) per free pose, the 3 world coordinates per landmark), with the session's Huber scale
+ * as the linearisation applies it and lambda * I added to every pose and landmark block: `lambda`
+ * is this call's argument, not the problem's; 0 gives the Gauss-Newton covariance.  A landmark
+ * whose 3x3 block V_p fails the pivot test is frozen and leaves the system, as in every step.  S is
+ * the reduced camera system of that linearisation (vo_ba_gn_step's S_out under `lambda`),
+ * F = n_poses - n_fixed, W_o = J_pose^T J_point of observation o.  Outputs, any may be NULL:
+ *   pose_dense_out (6F, 6F) row-major: Sigma_cc = S^-1; one triangle is computed and mirrored, so
+ *     it is symmetric bit for bit;
+ *   pose_cov_out (F, 6, 6): the diagonal blocks of Sigma_cc, the same bits;
+ *   point_cov_out (n_points, 3, 3), in the problem's landmark order:
+ *     Sigma_pp = V_p^-1 + T_p Sigma_cc T_p^T, where T_p (3 x 6F) holds in the columns of free
+ *     camera f the sum over p's observations o in f of (W_o V_p^-1)^T (duplicate observations
+ *     add; fixed cameras enter V_p only, so a landmark seen by fixed cameras alone has
+ *     V_p^-1); each block symmetric bit for bit; nine NaNs for a frozen landmark.
+ * Nothing is solved and nothing but the pending update is written: poses and points are
+ * afterwards what they were, and every later vo_ba_run* gives the bits it would have given
+ * without this call.  All sums run in a fixed order: two calls at one state agree bit for bit.
+ * VO_ERR_NOT_SPD: S is not positive definite; the requested outputs are filled with NaN and the
+ * session stays usable.  VO_ERR_ARG: lambda negative or not finite, or more than 567 free poses
+ * (the solve kernels keep 6F x 6 doubles in the 160 KiB of LDS).  VO_ERR_STATE: a stale session,
+ * no state set, or a communicator of more than one rank (covariance over landmark shards is not
+ * built). */
+int vo_ba_covariance(vo_ctx* ctx, uint64_t session, double lambda, double* pose_cov_out, double* pose_dense_out,
+                     double* point_cov_out);
 /* One-call convenience: setup + set_state + run + get_state. */
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points,
                 int iters, double* cost_out);

@@ -111,6 +111,7 @@ SIGNATURES = {
     "vo_ba_lm_stop_info": (_I, [_P, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vo_ba_set_robust": (_I, [_P, C.c_uint64, _D]),
     "vo_ba_residuals": (_I, [_P, C.c_uint64, _PD, _PD]),
+    "vo_ba_covariance": (_I, [_P, C.c_uint64, _D, _PD, _PD, _PD]),
     "vo_ba_solve": (_I, [_P, C.POINTER(BAProblemC), _PD, _PD, _I, _PD]),
     "vo_ba_plan_stats": (_I, [_P, _PI64, _I]),
     "vo_ba_debug_stamps": (_I, [_P, C.POINTER(C.c_uint64), _I]),

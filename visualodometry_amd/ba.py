@@ -28,6 +28,13 @@ non-increasing cost, not a smaller error against ground truth (``tests/ba_lm_ref
 loop on the oracle).  ``lm_ftol`` / ``lm_xtol`` / ``lm_max_rejects`` (``cfg.ba_lm_*``) end the loop
 on the device once it has converged or keeps rejecting (``vo_ba_set_lm_stop``;
 ``tests/ba_lm_stop_ref.py``); ``BAResult.lm_trials`` / ``lm_stop`` say how it ended.
+
+Covariance (off by default): ``BASession.covariance()`` / ``optimize(..., return_covariance=True)``
+(or ``cfg.ba_covariance``) read out the covariance of the free poses and of every landmark at the
+device state (``vo_ba_covariance``: the dense inverse of the reduced camera system and the 3x3
+landmark blocks, for unit pixel variance; ``tests/ba_cov_ref.py`` restates it on the oracle).  The
+weakly constrained, low-parallax landmarks are the ones with a huge variance; no culling policy
+is built on it.
 """
 
 from __future__ import annotations
@@ -75,6 +82,14 @@ class BAResult:
     # termination criterion that stopped it: "ftol", "xtol", "rejects"
     lm_trials: int | None = None
     lm_stop: str | None = None
+    # optimize(return_covariance=True): the Gauss-Newton covariance at the returned state for unit
+    # pixel variance -- pose_cov (F,6,6) over the free poses' left twists (rho, phi), point_cov
+    # (L,3,3) in the window's landmark order (NaN for a frozen landmark) -- and cov_sigma2, the
+    # variance estimate to scale both by: final cost / max(1, 2M - 6F - 3 (non-frozen landmarks)).
+    # None when not asked for, or when the reduced system was not positive definite.
+    pose_cov: np.ndarray | None = None
+    point_cov: np.ndarray | None = None
+    cov_sigma2: float | None = None
 
 
 def poses_to_rt(poses_cw: np.ndarray) -> np.ndarray:
@@ -249,6 +264,22 @@ class BASession:
                                            ptr(depth, C.c_double)), "vo_ba_residuals")
         return err2, depth
 
+    def covariance(self, lam: float = 0.0, dense: bool = False):
+        """``(pose_cov (F,6,6), point_cov (L,3,3))`` at the device state for unit pixel variance
+        (``vo_ba_covariance``; the caller scales by its sigma^2), plus the dense ``(6F,6F)`` pose
+        covariance when ``dense``.  ``lam`` is the damping of this linearisation (0: the
+        Gauss-Newton covariance).  A frozen landmark's block is NaN.  Raises ``VoError`` with
+        ``code == VO_ERR_NOT_SPD`` when the reduced camera system is not positive definite (the
+        session stays usable)."""
+        F = self.n_poses - self.n_fixed
+        pose = np.empty((F, 6, 6))
+        pts = np.empty((self.n_points, 3, 3))
+        full = np.empty((6 * F, 6 * F)) if dense else None
+        rc = self.ctx.lib.vo_ba_covariance(self.ctx.handle, self.session, float(lam), ptr(pose, C.c_double),
+                                           ptr(full, C.c_double) if dense else None, ptr(pts, C.c_double))
+        check(rc, "vo_ba_covariance")
+        return (pose, pts, full) if dense else (pose, pts)
+
     def set_state(self, poses_cw: np.ndarray, points: np.ndarray) -> None:
         rt = np.ascontiguousarray(poses_to_rt(poses_cw))
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
@@ -365,7 +396,7 @@ class BASession:
 class SlidingWindowBA:
     """``SlidingWindowBA(K, cfg).optimize(window) -> BAResult``.
 
-    ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda`` / ``ba_huber`` / ``ba_lm``; any
+    ``cfg`` may be a ``VOConfig`` carrying ``ba_iters`` / ``ba_lambda`` / ``ba_huber`` / ``ba_lm`` / ``ba_covariance``; any
     missing knob takes the keyword default.  ``lm`` (``cfg.ba_lm``): Levenberg-Marquardt step
     control on the device, ``lam`` its starting damping, ``lm_ftol`` / ``lm_xtol`` / ``lm_max_rejects``
     (``cfg.ba_lm_ftol`` / ``ba_lm_xtol`` / ``ba_lm_max_rejects``, all 0: off) its termination
@@ -376,7 +407,7 @@ class SlidingWindowBA:
 
     def __init__(self, K, cfg=None, *, iters: int = 10, lam: float = 0.0, huber: float = 0.0,
                  device: int | None = None, lm: bool = False, lm_ftol: float = 0.0, lm_xtol: float = 0.0,
-                 lm_max_rejects: int = 0):
+                 lm_max_rejects: int = 0, covariance: bool = False):
         self.K = np.asarray(K, dtype=np.float64)
         self.iters = int(getattr(cfg, "ba_iters", iters))
         self.lam = float(getattr(cfg, "ba_lambda", lam))
@@ -393,6 +424,8 @@ class SlidingWindowBA:
         if not (0.0 <= self.lm_ftol < 1.0 and np.isfinite(self.lm_xtol) and self.lm_xtol >= 0.0
                 and self.lm_max_rejects >= 0):
             raise ValueError("ba_lm_ftol must be in [0, 1), ba_lm_xtol finite and >= 0, ba_lm_max_rejects >= 0")
+        # covariance read-out of every optimize() (cfg.ba_covariance); off by default
+        self.covariance = bool(getattr(cfg, "ba_covariance", covariance))
         self.device = device
 
     def reserve(self, n_poses: int, n_points: int, obs_per_point: float = 5.0, n_fixed: int = 2) -> None:
@@ -403,7 +436,7 @@ class SlidingWindowBA:
         n_obs = max(2 * n_points, int(round(obs_per_point * n_points)))
         _lib.ba_reserve(_lib.context(self.device), max(2, int(n_poses)), n_points, n_obs, int(n_fixed))
 
-    def optimize(self, window: BAWindow, return_residuals: bool = False) -> BAResult:
+    def optimize(self, window: BAWindow, return_residuals: bool = False, return_covariance: bool = False) -> BAResult:
         poses = np.asarray(window.poses_cw, dtype=np.float64)
         pts = np.asarray(window.points, dtype=np.float64).reshape(-1, 3)
         n_fixed = min(int(window.n_fixed), poses.shape[0])
@@ -412,7 +445,7 @@ class SlidingWindowBA:
             return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", "empty window")
         point_ptr, obs_cam, obs_uv, order = group_window(pts.shape[0], window, return_order=True)
         ctx = _lib.context(self.device)
-        err2 = depth = None
+        err2 = depth = pose_cov = point_cov = sigma2 = None
         try:
             sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
                              huber=self.huber)
@@ -433,10 +466,22 @@ class SlidingWindowBA:
                     e, d = np.empty_like(err2), np.empty_like(depth)
                     e[order], d[order] = err2, depth
                     err2, depth = e, d
+            if (return_covariance or self.covariance) and rc == _lib.VO_OK:
+                # the Gauss-Newton covariance (no damping) at the returned state; landmarks keep
+                # the window's own indices (grouping reorders observations only)
+                try:
+                    pose_cov, point_cov = sess.covariance(0.0)
+                    live = int(np.isfinite(point_cov[:, 0, 0]).sum())
+                    dof = 2 * obs_cam.size - 6 * (poses.shape[0] - n_fixed) - 3 * live
+                    sigma2 = float(costs[-1]) / max(1, dof)
+                except VoError as e:
+                    if e.code != _lib.VO_ERR_NOT_SPD:
+                        raise
+                    pose_cov = point_cov = sigma2 = None
         except VoError as e:
             if e.code == _lib.VO_ERR_ARG:
                 return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", str(e))
             raise
         status = "ok" if rc == _lib.VO_OK else "not_spd"
         return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth, lambdas=lambdas, accepted=accepted,
-                        lm_trials=lm_trials, lm_stop=lm_stop)
+                        lm_trials=lm_trials, lm_stop=lm_stop, pose_cov=pose_cov, point_cov=point_cov, cov_sigma2=sigma2)

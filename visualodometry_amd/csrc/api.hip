@@ -807,6 +807,17 @@ int vo_ba_residuals(vo_ctx* ctx, uint64_t session, double* err2_out, double* dep
   });
 }
 
+int vo_ba_covariance(vo_ctx* ctx, uint64_t session, double lambda, double* pose_cov_out, double* pose_dense_out,
+                     double* point_cov_out) {
+  int rc = VO_OK;
+  int g = guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    rc = vo::ba_covariance(ctx, lambda, pose_cov_out, pose_dense_out, point_cov_out);
+  });
+  return g != VO_OK ? g : rc;
+}
+
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points, int iters,
                 double* cost_out) {
   uint64_t s = 0;

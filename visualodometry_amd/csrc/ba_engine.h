@@ -24,6 +24,7 @@ void ba_set_lm_stop(vo_ctx* ctx, const vo_ba_lm_stop* stop);
 void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason);
 void ba_set_robust(vo_ctx* ctx, double huber_delta);
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
+int ba_covariance(vo_ctx* ctx, double lambda, double* pose_cov, double* pose_dense, double* point_cov);
 int ba_stats(vo_ctx* ctx, int64_t* out, int n);
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n);
 int ba_chain_stamps(vo_ctx* ctx, uint64_t* out, int n);

@@ -13,6 +13,7 @@
 
 #include "ba_band.h"
 #include "ba_comm.h"
+#include "ba_cov.h"
 #include "ba_kernels.h"
 #include "ba_plan.h"
 #include "vo_ctx.h"
@@ -181,6 +182,7 @@ class BAEngine {
     lm_iters_ = -1;  // without an LM log
     lm_stop_ = vo_ba_lm_stop{};  // and with an LM loop that never stops early
     obs_uploaded_ = false;
+    cov_uploaded_ = false;
     session_ = ++g_ba_sessions;
     return session_;
   }
@@ -306,23 +308,7 @@ class BAEngine {
     hipStream_t st = ctx_->stream;
     const size_t M = (size_t)P.n_obs;
     if (M == 0) return;
-    if (!obs_uploaded_) {
-      std::vector<int32_t> cam(M), pt(M);
-      std::vector<float> uv(2 * M);
-      VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "vo_ba_residuals: the plan has no observation order");
-      for (size_t pos = 0; pos < M; ++pos) {  // internal position -> problem observation (ba_plan.h)
-        const size_t o = (size_t)P.obs_order[pos];
-        cam[o] = P.obs_cam[pos];
-        pt[o] = P.te_pt[P.obs_te[pos]];
-        uv[2 * o] = P.obs_uv[2 * pos];
-        uv[2 * o + 1] = P.obs_uv[2 * pos + 1];
-      }
-      upload(d_obs_cam_, cam, st);
-      upload(d_obs_pt_, pt, st);
-      upload(d_obs_uv_, uv, st);
-      VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
-      obs_uploaded_ = true;
-    }
+    upload_obs();
     d_obs_out_.reserve(2 * M * 8);
     ObsResidualArgs A;
     A.n_obs = (int)M;
@@ -339,6 +325,159 @@ class BAEngine {
     if (err2_out) VO_HIP_CHECK(hipMemcpyAsync(err2_out, A.err2, M * 8, hipMemcpyDeviceToHost, st));
     if (depth_out) VO_HIP_CHECK(hipMemcpyAsync(depth_out, A.depth, M * 8, hipMemcpyDeviceToHost, st));
     VO_HIP_CHECK(hipStreamSynchronize(st));
+  }
+
+  // Pose and landmark covariance at the device state (include/vo_hip.h vo_ba_covariance, DESIGN.md
+  // §Covariance): K1 in accumulate mode and the stand-alone K2 under this call's lambda leave S in
+  // d_sys_ (nothing is solved; the problem's lambda, the status word, the LM state and the state
+  // itself are not written), then ba_cov.hip's kernels invert S densely and form the landmark
+  // blocks.  Any output may be null.
+  int covariance(double lambda, double* pose_cov_out, double* pose_dense_out, double* point_cov_out) {
+    require_state();
+    VO_REQUIRE(std::isfinite(lambda) && lambda >= 0.0, VO_ERR_ARG, "vo_ba_covariance: lambda must be finite and >= 0");
+    VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_covariance: not with a communicator of more than one rank");
+    const BAPlan& P = plan_;
+    const int F = P.n_free, L = P.n_points;
+    const size_t n = 6ull * F;
+    VO_REQUIRE(cov_solve_lds_bytes(F) <= kCovSolveLdsMax, VO_ERR_ARG,
+               "vo_ba_covariance: %d free poses exceed the solve kernel's LDS", F);
+    hipStream_t st = ctx_->stream;
+    apply_pending();
+    upload_cov_tables();
+    int fail = 0;
+    if (F > 0) {
+      // the system: enqueue_lin / enqueue_reduce without their profiler brackets, status tests and
+      // LM damping
+      if (P.n_segments() > 0) {
+        LinArgs A = lin_args();
+        A.lambda = lambda;
+        A.lm_lambda = nullptr;
+        A.status = nullptr;
+        A.nseg = P.n_segments();
+        const bool wave = plan_is_wave(P.seg_obs);
+        launch_lin(A, huber_ > 0.0 ? kAccum | kRobust : kAccum, wave ? P.seg_chunks : 0, A.nseg, st);
+        VO_HIP_CHECK(hipGetLastError());
+      } else {
+        VO_HIP_CHECK(hipMemsetAsync(d_slab_cost_.ptr, 0, 8, st));
+      }
+      ReduceArgs R = reduce_args();
+      R.lambda = lambda;
+      R.lm_lambda = nullptr;
+      R.status = nullptr;
+      launch_reduce(R, R.nprof + 1, st);
+      VO_HIP_CHECK(hipGetLastError());
+      d_cov_l_.reserve(n * n * 8);
+      d_cov_.reserve(n * n * 8);
+      VO_HIP_CHECK(hipMemsetAsync(d_cov_l_.ptr, 0, n * n * 8, st));
+      CovPoseArgs C;
+      C.F = F;
+      C.first = d_cov_first_.as<int>();
+      C.off = d_cov_off_.as<int>();
+      C.last = d_cov_last_.as<int>();
+      C.dst = d_cov_dst_.as<int>();
+      C.sys = d_sys_.as<double>();
+      C.L = d_cov_l_.as<double>();
+      C.cov = d_cov_.as<double>();
+      C.fail = d_cov_fail_.as<int>();
+      launch_cov_factor(C, st);
+      VO_HIP_CHECK(hipGetLastError());
+      launch_cov_solve(C, st);
+      VO_HIP_CHECK(hipGetLastError());
+      VO_HIP_CHECK(hipMemcpyAsync(&fail, C.fail, sizeof(int), hipMemcpyDeviceToHost, st));
+      VO_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (fail) {
+      if (pose_cov_out) std::fill(pose_cov_out, pose_cov_out + 36ull * F, (double)NAN);
+      if (pose_dense_out) std::fill(pose_dense_out, pose_dense_out + n * n, (double)NAN);
+      if (point_cov_out) std::fill(point_cov_out, point_cov_out + 9ull * L, (double)NAN);
+      set_error("vo_ba_covariance: reduced camera system not positive definite at block column %d", fail - 1);
+      return VO_ERR_NOT_SPD;
+    }
+    if (point_cov_out && L > 0) {
+      d_cov_pts_.reserve(9ull * L * 8);
+      CovPointArgs Q;
+      Q.n_points = L;
+      Q.n_fixed = P.n_fixed;
+      Q.F = F;
+      Q.fx = prob_.fx; Q.fy = prob_.fy; Q.cx = prob_.cx; Q.cy = prob_.cy;
+      Q.lambda = lambda;
+      Q.huber = huber_;
+      Q.huber2 = huber_ * huber_;
+      Q.point_ptr = d_cov_ptr_.as<int>();
+      Q.pt_inv = d_cov_inv_.as<int>();
+      Q.obs_cam = d_obs_cam_.as<int>();
+      Q.obs_uv = d_obs_uv_.as<float2>();
+      Q.poses = d_pose_[cur_].as<double>();
+      Q.points = d_points_.as<double>();
+      Q.cov = d_cov_.as<double>();
+      Q.out = d_cov_pts_.as<double>();
+      launch_cov_points(Q, st);
+      VO_HIP_CHECK(hipGetLastError());
+      VO_HIP_CHECK(hipMemcpyAsync(point_cov_out, Q.out, 9ull * L * 8, hipMemcpyDeviceToHost, st));
+    }
+    std::vector<double> tmp;
+    const double* dense = pose_dense_out;
+    if (F > 0 && (pose_dense_out || pose_cov_out)) {
+      if (!pose_dense_out) tmp.resize(n * n);
+      double* dst = pose_dense_out ? pose_dense_out : tmp.data();
+      dense = dst;
+      VO_HIP_CHECK(hipMemcpyAsync(dst, d_cov_.ptr, n * n * 8, hipMemcpyDeviceToHost, st));
+    }
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    if (pose_cov_out)  // the diagonal blocks, copied from the dense matrix
+      for (int f = 0; f < F; ++f)
+        for (int r = 0; r < 6; ++r)
+          std::copy(dense + (6ull * f + r) * n + 6ull * f, dense + (6ull * f + r) * n + 6ull * f + 6,
+                    pose_cov_out + 36ull * f + 6 * r);
+    return VO_OK;
+  }
+
+  // covariance()'s tables, sent on a session's first call: the profile of S and K2's block
+  // offsets, the problem-order CSR (rebuilt from the plan like upload_obs's arrays) and the
+  // problem landmark -> internal landmark map.
+  void upload_cov_tables() {
+    upload_obs();
+    if (cov_uploaded_) return;
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const size_t M = (size_t)P.n_obs;
+    std::vector<int32_t> ptr(P.n_points + 1, 0), inv(std::max(1, P.n_points), 0);
+    for (int q = 0; q < P.n_points; ++q) inv[P.pt_perm[q]] = q;
+    for (size_t pos = 0; pos < M; ++pos) ++ptr[P.pt_perm[P.te_pt[P.obs_te[pos]]] + 1];
+    for (int p = 0; p < P.n_points; ++p) ptr[p + 1] += ptr[p];
+    upload(d_cov_ptr_, ptr, st);
+    upload(d_cov_inv_, inv, st);
+    upload(d_cov_first_, P.prof_first, st);
+    upload(d_cov_off_, P.prof_off, st);
+    upload(d_cov_last_, P.prof_last, st);
+    upload(d_cov_dst_, red_dst_, st);
+    d_cov_fail_.reserve(sizeof(int));
+    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
+    cov_uploaded_ = true;
+  }
+
+  // The problem-order observation arrays of residuals() and covariance(), sent on a session's
+  // first use: rebuilt from the plan's internal-order copies (the caller's arrays are not kept).
+  void upload_obs() {
+    if (obs_uploaded_) return;
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const size_t M = (size_t)P.n_obs;
+    std::vector<int32_t> cam(M), pt(M);
+    std::vector<float> uv(2 * M);
+    VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "BA read-out: the plan has no observation order");
+    for (size_t pos = 0; pos < M; ++pos) {  // internal position -> problem observation (ba_plan.h)
+      const size_t o = (size_t)P.obs_order[pos];
+      cam[o] = P.obs_cam[pos];
+      pt[o] = P.te_pt[P.obs_te[pos]];
+      uv[2 * o] = P.obs_uv[2 * pos];
+      uv[2 * o + 1] = P.obs_uv[2 * pos + 1];
+    }
+    upload(d_obs_cam_, cam, st);
+    upload(d_obs_pt_, pt, st);
+    upload(d_obs_uv_, uv, st);
+    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
+    obs_uploaded_ = true;
   }
 
   // iters GN iterations; sync=true finalises and reads the costs back.
@@ -1253,6 +1392,11 @@ class BAEngine {
   // its output [err2 | depth]
   bool obs_uploaded_ = false;
   DevBuf d_obs_cam_, d_obs_pt_, d_obs_uv_, d_obs_out_;
+  // covariance(): its tables (uploaded on a session's first call), the dense factor and inverse
+  // of S, the landmark blocks and the factorisation's failure word
+  bool cov_uploaded_ = false;
+  DevBuf d_cov_ptr_, d_cov_inv_, d_cov_first_, d_cov_off_, d_cov_last_, d_cov_dst_;
+  DevBuf d_cov_l_, d_cov_, d_cov_pts_, d_cov_fail_;
 };
 
 // ---- entry points used by api.hip -------------------------------------------------
@@ -1284,6 +1428,9 @@ void ba_set_lm_stop(vo_ctx* ctx, const vo_ba_lm_stop* stop) { ba_engine(ctx)->se
 void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason) { ba_engine(ctx)->lm_stop_info(trials, reason); }
 void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta); }
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }
+int ba_covariance(vo_ctx* ctx, double lambda, double* pose_cov, double* pose_dense, double* point_cov) {
+  return ba_engine(ctx)->covariance(lambda, pose_cov, pose_dense, point_cov);
+}
 int ba_stats(vo_ctx* ctx, int64_t* out, int n) { return ba_engine(ctx)->stats(out, n); }
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_stamps(out, n); }
 int ba_chain_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_chain_stamps(out, n); }

@@ -55,6 +55,7 @@ class VOConfig:
     ba_lm_ftol: float = 0.0  # stop once an accepted step lowers the cost by at most this fraction
     ba_lm_xtol: float = 0.0  # stop once an accepted step's largest pose-update entry is at most this
     ba_lm_max_rejects: int = 0  # stop after this many rejected steps in a row
+    ba_covariance: bool = False  # also read out the pose and landmark covariance of each adjusted window
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)

@@ -192,7 +192,9 @@ def run_window_ba(vo, win: KeyframeWindow):
     if ba is None:
         ba = SlidingWindowBA(vo.K, cfg)
         vo._vo_amd_ba = ba
-    res = ba.optimize(window)
+    # cfg.ba_covariance: the result (kept on vo._vo_amd_last_ba) also carries the pose and landmark
+    # covariance of the adjusted window; no policy here reads it
+    res = ba.optimize(window, return_covariance=True) if getattr(cfg, "ba_covariance", False) else ba.optimize(window)
     if res.status != "ok" or not np.all(np.isfinite(res.cost_per_iter)) or \
             res.cost_per_iter[-1] > res.cost_per_iter[0]:
         print(f"BA: window rejected ({res.status} {res.message})")
