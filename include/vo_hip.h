@@ -329,6 +329,55 @@ int vo_ba_residuals(vo_ctx* ctx, uint64_t session, double* err2_out, double* dep
  * built). */
 int vo_ba_covariance(vo_ctx* ctx, uint64_t session, double lambda, double* pose_cov_out, double* pose_dense_out,
                      double* point_cov_out);
+/* Observation weights.  Every observation o has an information weight w_o >= 0 (1 / sigma^2 in
+ * pixels^-2), 1 after every vo_ba_setup.  With r, J_pose, J_point the raw residual and Jacobians:
+ *   w_o > 0: the linearisation uses sqrt(w_o) r, sqrt(w_o) J_pose, sqrt(w_o) J_point; the session's
+ *     Huber rule, if any, is applied to the whitened residual (n^2 = w_o r.r against delta^2, the
+ *     Huber scale multiplying on top), and the observation's cost term is rho(w_o r.r), which is
+ *     w_o r.r without Huber.  sqrt(w_o) is taken once on the host (IEEE double); the device only
+ *     multiplies.
+ *   w_o == 0: the observation is inactive and contributes exact zeros to the cost, V, W, S, b and
+ *     g -- by a select, not a product, so an inactive observation whose raw residual is not finite
+ *     (zero or negative depth) turns no sum into NaN.
+ * A landmark its active observations no longer support is frozen by the pivot test as ever (at
+ * lambda = 0; under damping it stays put).  vo_ba_residuals stays raw and unweighted;
+ * vo_ba_covariance honours the weights (H = J^T W J, the Huber scale on the whitened residual).
+ * vo_ba_set_obs_weights: w holds n_obs weights in the order of vo_ba_problem.obs_cam; NULL restores
+ * all ones.  Valid any time after vo_ba_setup; a pending vo_ba_gn_step's landmark update is applied
+ * first, under the weights it was solved with.  While a session has no weights (after vo_ba_setup,
+ * and after NULL until a cull) every launch is the one a session without this feature makes; with
+ * weights, K1 is always a launch of its own (never inside the solve launch), and a K1 layout
+ * without a weighted form (the four-wave K1 of the testing switch) fails the run with
+ * VO_ERR_STATE.  VO_ERR_ARG: a negative or non-finite weight, and nothing is changed.
+ * VO_ERR_STATE: a stale session, or a communicator of more than one rank (weights over landmark
+ * shards are not built).
+ * vo_ba_get_obs_weights: synchronises and returns the current weights in problem order: what was
+ * set, the culled observations at 0. */
+int vo_ba_set_obs_weights(vo_ctx* ctx, uint64_t session, const double* w);
+int vo_ba_get_obs_weights(vo_ctx* ctx, uint64_t session, double* w_out);
+/* Device-side outlier culling at the device-resident state (after any pending landmark update).
+ * With err2_o and z_o the values vo_ba_residuals reports there (the same arithmetic), an active
+ * observation is deactivated (w_o := 0) iff
+ *   max_chi2 > 0 and w_o * err2_o > max_chi2,  or  z_o <= min_depth,  or  err2_o or z_o is not finite;
+ * then every landmark with fewer than min_track active observations loses all of them
+ * (min_track <= 0: not tested; the sensible value is 2).  A culled observation comes back only
+ * through vo_ba_set_obs_weights.  Nothing else is written: poses, points, the LM log and the
+ * status word stay as they were, and a second cull at the same state with the same options culls
+ * nothing.  n_culled_out: observations this call deactivated; n_active_out: observations active
+ * after it (either may be NULL).  vo_ba_cull_async enqueues the same kernels on the context
+ * stream without any host synchronisation, so run_lm_async, cull_async, run_lm_async, ... makes no
+ * round trip; its outcome is read with vo_ba_get_obs_weights.  VO_ERR_ARG: a non-finite field,
+ * max_chi2 < 0 or reserved != 0.  VO_ERR_STATE: a stale session, no state set, or a communicator
+ * of more than one rank. */
+typedef struct {
+  double max_chi2;   /* 0: not tested */
+  double min_depth;
+  int32_t min_track; /* <= 0: not tested */
+  int32_t reserved;  /* 0 */
+} vo_ba_cull_options;
+int vo_ba_cull(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt, int32_t* n_culled_out,
+               int32_t* n_active_out);
+int vo_ba_cull_async(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt);
 /* One-call convenience: setup + set_state + run + get_state. */
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points,
                 int iters, double* cost_out);

@@ -52,6 +52,12 @@ class BALmStopC(C.Structure):
     _fields_ = [("ftol", C.c_double), ("xtol", C.c_double), ("max_rejects", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BACullOptionsC(C.Structure):
+    """``vo_ba_cull_options``: ``max_chi2`` 0 and ``min_track`` <= 0 are not tested."""
+    _fields_ = [("max_chi2", C.c_double), ("min_depth", C.c_double), ("min_track", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # vo_ba_lm_stop_info's reasons (VO_BA_LM_*)
 BA_LM_FAILED, BA_LM_RAN_ALL, BA_LM_FTOL, BA_LM_XTOL, BA_LM_REJECTS = -1, 0, 1, 2, 3
 BA_LM_REASONS = {BA_LM_FAILED: "failed", BA_LM_RAN_ALL: "ran_all", BA_LM_FTOL: "ftol", BA_LM_XTOL: "xtol",
@@ -112,6 +118,10 @@ SIGNATURES = {
     "vo_ba_set_robust": (_I, [_P, C.c_uint64, _D]),
     "vo_ba_residuals": (_I, [_P, C.c_uint64, _PD, _PD]),
     "vo_ba_covariance": (_I, [_P, C.c_uint64, _D, _PD, _PD, _PD]),
+    "vo_ba_set_obs_weights": (_I, [_P, C.c_uint64, _PD]),
+    "vo_ba_get_obs_weights": (_I, [_P, C.c_uint64, _PD]),
+    "vo_ba_cull": (_I, [_P, C.c_uint64, C.POINTER(BACullOptionsC), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "vo_ba_cull_async": (_I, [_P, C.c_uint64, C.POINTER(BACullOptionsC)]),
     "vo_ba_solve": (_I, [_P, C.POINTER(BAProblemC), _PD, _PD, _I, _PD]),
     "vo_ba_plan_stats": (_I, [_P, _PI64, _I]),
     "vo_ba_debug_stamps": (_I, [_P, C.POINTER(C.c_uint64), _I]),

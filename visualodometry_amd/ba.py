@@ -35,6 +35,16 @@ device state (``vo_ba_covariance``: the dense inverse of the reduced camera syst
 landmark blocks, for unit pixel variance; ``tests/ba_cov_ref.py`` restates it on the oracle).  The
 weakly constrained, low-parallax landmarks are the ones with a huge variance; no culling policy
 is built on it.
+
+Observation weights and culling (off by default): ``BAWindow.obs_weight`` /
+``BASession.set_obs_weights`` give every observation an information weight (1 / sigma^2; 0: it does
+not count), applied as ``sqrt(w)`` on the residual and Jacobians ahead of the Huber rule.
+``BASession.cull`` / ``cull_async`` deactivate, on the device and without a new setup, the
+observations with ``w * err2 > max_chi2``, a depth at or below ``min_depth`` or a non-finite
+residual, then the tracks left shorter than ``min_track``.  ``cull_rounds = R`` (``cfg.ba_cull_rounds``,
+with ``ba_cull_chi2`` / ``ba_cull_min_depth``) makes ``optimize`` run ``R + 1`` solves with a cull
+between them; ``BAResult.obs_active`` says what survived (``tests/ba_weight_ref.py`` restates both on
+the oracle).
 """
 
 from __future__ import annotations
@@ -44,7 +54,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BALmOptionsC, BALmStopC, BAProblemC, C, VoError, check, ptr
+from ._lib import BACullOptionsC, BALmOptionsC, BALmStopC, BAProblemC, C, VoError, check, ptr
 
 
 @dataclass
@@ -61,6 +71,9 @@ class BAWindow:
     obs_cam: np.ndarray  # (M,) int
     obs_pt: np.ndarray  # (M,) int
     n_fixed: int = 2
+    # (M,) information weights (1 / sigma^2, px^-2) in the window's own observation order, 0 for an
+    # observation that does not count; None: all ones
+    obs_weight: np.ndarray | None = None
 
 
 @dataclass
@@ -90,6 +103,9 @@ class BAResult:
     pose_cov: np.ndarray | None = None
     point_cov: np.ndarray | None = None
     cov_sigma2: float | None = None
+    # culling (cull_rounds > 0): which observations were still active after the last solve, in the
+    # window's own observation order; cost_per_iter then concatenates the parts' costs
+    obs_active: np.ndarray | None = None
 
 
 def poses_to_rt(poses_cw: np.ndarray) -> np.ndarray:
@@ -264,6 +280,42 @@ class BASession:
                                            ptr(depth, C.c_double)), "vo_ba_residuals")
         return err2, depth
 
+    def set_obs_weights(self, w) -> None:
+        """Information weights (1 / sigma^2, px^-2) per observation in the order of ``obs_cam``
+        (``vo_ba_set_obs_weights``); 0 deactivates an observation, ``None`` restores all ones."""
+        if w is None:
+            check(self.ctx.lib.vo_ba_set_obs_weights(self.ctx.handle, self.session, None), "vo_ba_set_obs_weights")
+            return
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        if w.size != self.obs_cam.size:
+            raise ValueError("one weight per observation expected")
+        check(self.ctx.lib.vo_ba_set_obs_weights(self.ctx.handle, self.session, ptr(w, C.c_double)),
+              "vo_ba_set_obs_weights")
+
+    def obs_weights(self) -> np.ndarray:
+        """Synchronises; the current weights in the order of ``obs_cam``, culled observations at 0."""
+        w = np.empty(self.obs_cam.size)
+        check(self.ctx.lib.vo_ba_get_obs_weights(self.ctx.handle, self.session, ptr(w, C.c_double)),
+              "vo_ba_get_obs_weights")
+        return w
+
+    def cull(self, max_chi2: float = 0.0, min_depth: float = 0.0, min_track: int = 2):
+        """Deactivates, on the device and at the device state, every active observation with
+        ``w * err2 > max_chi2`` (``max_chi2`` 0: not tested), depth ``<= min_depth`` or a non-finite
+        residual, then what is left of every track shorter than ``min_track`` (``vo_ba_cull``);
+        returns ``(n_culled, n_active)``."""
+        opt = BACullOptionsC(float(max_chi2), float(min_depth), int(min_track), 0)
+        culled, active = C.c_int32(0), C.c_int32(0)
+        check(self.ctx.lib.vo_ba_cull(self.ctx.handle, self.session, C.byref(opt), C.byref(culled), C.byref(active)),
+              "vo_ba_cull")
+        return int(culled.value), int(active.value)
+
+    def cull_async(self, max_chi2: float = 0.0, min_depth: float = 0.0, min_track: int = 2) -> None:
+        """:meth:`cull` enqueued on the context stream without a host synchronisation; its outcome
+        is read with :meth:`obs_weights`."""
+        opt = BACullOptionsC(float(max_chi2), float(min_depth), int(min_track), 0)
+        check(self.ctx.lib.vo_ba_cull_async(self.ctx.handle, self.session, C.byref(opt)), "vo_ba_cull_async")
+
     def covariance(self, lam: float = 0.0, dense: bool = False):
         """``(pose_cov (F,6,6), point_cov (L,3,3))`` at the device state for unit pixel variance
         (``vo_ba_covariance``; the caller scales by its sigma^2), plus the dense ``(6F,6F)`` pose
@@ -407,7 +459,8 @@ class SlidingWindowBA:
 
     def __init__(self, K, cfg=None, *, iters: int = 10, lam: float = 0.0, huber: float = 0.0,
                  device: int | None = None, lm: bool = False, lm_ftol: float = 0.0, lm_xtol: float = 0.0,
-                 lm_max_rejects: int = 0, covariance: bool = False):
+                 lm_max_rejects: int = 0, covariance: bool = False, cull_rounds: int = 0, cull_chi2: float = 0.0,
+                 cull_min_depth: float = 0.0):
         self.K = np.asarray(K, dtype=np.float64)
         self.iters = int(getattr(cfg, "ba_iters", iters))
         self.lam = float(getattr(cfg, "ba_lambda", lam))
@@ -426,6 +479,15 @@ class SlidingWindowBA:
             raise ValueError("ba_lm_ftol must be in [0, 1), ba_lm_xtol finite and >= 0, ba_lm_max_rejects >= 0")
         # covariance read-out of every optimize() (cfg.ba_covariance); off by default
         self.covariance = bool(getattr(cfg, "ba_covariance", covariance))
+        # device-side culling (cfg.ba_cull_*): cull_rounds = R > 0 runs R + 1 solves of `iters` each
+        # with a cull between them (w * err2 > cull_chi2, depth <= cull_min_depth, tracks shorter
+        # than 2); 0: off
+        self.cull_rounds = int(getattr(cfg, "ba_cull_rounds", cull_rounds))
+        self.cull_chi2 = float(getattr(cfg, "ba_cull_chi2", cull_chi2))
+        self.cull_min_depth = float(getattr(cfg, "ba_cull_min_depth", cull_min_depth))
+        if not (self.cull_rounds >= 0 and np.isfinite(self.cull_chi2) and self.cull_chi2 >= 0.0
+                and np.isfinite(self.cull_min_depth)):
+            raise ValueError("ba_cull_rounds must be >= 0, ba_cull_chi2 finite and >= 0, ba_cull_min_depth finite")
         self.device = device
 
     def reserve(self, n_poses: int, n_points: int, obs_per_point: float = 5.0, n_fixed: int = 2) -> None:
@@ -450,15 +512,39 @@ class SlidingWindowBA:
             sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
                              huber=self.huber)
             sess.set_state(poses, pts)
-            lambdas = accepted = lm_trials = lm_stop = None
+            if window.obs_weight is not None:
+                w = np.asarray(window.obs_weight, dtype=np.float64).reshape(-1)
+                if w.size != obs_cam.size:
+                    raise ValueError("obs_weight: one weight per observation expected")
+                sess.set_obs_weights(w if order is None else w[order])
+            lambdas = accepted = lm_trials = lm_stop = active = None
+            if self.lm and (self.lm_ftol or self.lm_xtol or self.lm_max_rejects):
+                sess.set_lm_stop(self.lm_ftol, self.lm_xtol, self.lm_max_rejects)
+            # cull_rounds + 1 solves with a cull between them (one solve without culling)
+            parts = []
+            for k in range(self.cull_rounds + 1):
+                if self.lm:
+                    rc, c, lams, _, acc = sess.run_lm(self.iters, lam0=self.lam)
+                    trials, reason = sess.lm_stop_info()
+                    parts.append((c, lams, acc, trials))
+                    lm_stop = _lib.BA_LM_REASONS[reason]
+                else:
+                    rc, c = sess.run(self.iters)
+                    parts.append((c,))
+                if rc != _lib.VO_OK or k == self.cull_rounds:
+                    break
+                sess.cull_async(self.cull_chi2, self.cull_min_depth, 2)
+            costs = np.concatenate([q[0] for q in parts])
             if self.lm:
-                if self.lm_ftol or self.lm_xtol or self.lm_max_rejects:
-                    sess.set_lm_stop(self.lm_ftol, self.lm_xtol, self.lm_max_rejects)
-                rc, costs, lambdas, _, accepted = sess.run_lm(self.iters, lam0=self.lam)
-                lm_trials, reason = sess.lm_stop_info()
-                lm_stop = _lib.BA_LM_REASONS[reason]
-            else:
-                rc, costs = sess.run(self.iters)
+                lambdas = np.concatenate([q[1] for q in parts])
+                accepted = np.concatenate([q[2] for q in parts])
+                lm_trials = int(sum(q[3] for q in parts))
+            if self.cull_rounds > 0:
+                active = sess.obs_weights() > 0
+                if order is not None:
+                    a = np.empty_like(active)
+                    a[order] = active
+                    active = a
             P, X = sess.get_state()
             if return_residuals:
                 err2, depth = sess.residuals()
@@ -472,7 +558,8 @@ class SlidingWindowBA:
                 try:
                     pose_cov, point_cov = sess.covariance(0.0)
                     live = int(np.isfinite(point_cov[:, 0, 0]).sum())
-                    dof = 2 * obs_cam.size - 6 * (poses.shape[0] - n_fixed) - 3 * live
+                    n_act = obs_cam.size if active is None else int(active.sum())  # culled ones left the system
+                    dof = 2 * n_act - 6 * (poses.shape[0] - n_fixed) - 3 * live
                     sigma2 = float(costs[-1]) / max(1, dof)
                 except VoError as e:
                     if e.code != _lib.VO_ERR_NOT_SPD:
@@ -484,4 +571,5 @@ class SlidingWindowBA:
             raise
         status = "ok" if rc == _lib.VO_OK else "not_spd"
         return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth, lambdas=lambdas, accepted=accepted,
-                        lm_trials=lm_trials, lm_stop=lm_stop, pose_cov=pose_cov, point_cov=point_cov, cov_sigma2=sigma2)
+                        lm_trials=lm_trials, lm_stop=lm_stop, pose_cov=pose_cov, point_cov=point_cov, cov_sigma2=sigma2,
+                        obs_active=active)

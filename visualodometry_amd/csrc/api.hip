@@ -818,6 +818,40 @@ int vo_ba_covariance(vo_ctx* ctx, uint64_t session, double lambda, double* pose_
   return g != VO_OK ? g : rc;
 }
 
+int vo_ba_set_obs_weights(vo_ctx* ctx, uint64_t session, const double* w) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_set_obs_weights(ctx, w);
+  });
+}
+
+int vo_ba_get_obs_weights(vo_ctx* ctx, uint64_t session, double* w_out) {
+  return guarded([&] {
+    vo::bind(ctx);
+    VO_REQUIRE(w_out, VO_ERR_ARG, "vo_ba_get_obs_weights: null output");
+    vo::ba_check_session(ctx, session);
+    vo::ba_get_obs_weights(ctx, w_out);
+  });
+}
+
+int vo_ba_cull(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt, int32_t* n_culled_out,
+               int32_t* n_active_out) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_cull(ctx, opt, n_culled_out, n_active_out, true);
+  });
+}
+
+int vo_ba_cull_async(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt) {
+  return guarded([&] {
+    vo::bind(ctx);
+    vo::ba_check_session(ctx, session);
+    vo::ba_cull(ctx, opt, nullptr, nullptr, false);
+  });
+}
+
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points, int iters,
                 double* cost_out) {
   uint64_t s = 0;

@@ -38,7 +38,8 @@ struct CovPointArgs {
   const double* poses;    // 12 per camera
   const double* points;   // 3 per landmark, internal order
   const double* cov;      // (6F, 6F) pose covariance
-  double* out;            // 9 per landmark, problem order; NaN for a frozen landmark
+  const double* sqrt_w;   // problem order: sqrt of the observation weights; null: a session without weights
+  double* out;          // 9 per landmark, problem order; NaN for a frozen landmark
 };
 void launch_cov_points(const CovPointArgs& A, hipStream_t st);
 

@@ -228,10 +228,23 @@ __device__ __forceinline__ void cov_obs_lin(const CovPointArgs& A, int o, int ca
   const double iz = rcp_nr(z);
   double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
   double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+  // observation weights: K1's order (obs_lin_w) -- sqrt(w) on the residual and the Jacobians, a
+  // zero weight a select, then the Huber rule on the whitened residual
+  const bool weighted = A.sqrt_w != nullptr;
+  const double sw = weighted ? A.sqrt_w[o] : 1.0;
+  const bool on = sw > 0.0;
+  if (weighted) {
+    j00 = on ? j00 * sw : 0.0; j02 = on ? j02 * sw : 0.0;
+    j11 = on ? j11 * sw : 0.0; j12 = on ? j12 * sw : 0.0;
+  }
   if (A.huber > 0.0) {
     const float2 m = A.obs_uv[o];
-    const double r0 = A.fx * x * iz + A.cx - (double)m.x;
-    const double r1 = A.fy * y * iz + A.cy - (double)m.y;
+    double r0 = A.fx * x * iz + A.cx - (double)m.x;
+    double r1 = A.fy * y * iz + A.cy - (double)m.y;
+    if (weighted) {
+      r0 = on ? r0 * sw : 0.0;
+      r1 = on ? r1 * sw : 0.0;
+    }
     double rho;
     const double s = huber_scale(r0, r1, A.huber, A.huber2, rho);
     j00 *= s; j02 *= s; j11 *= s; j12 *= s;

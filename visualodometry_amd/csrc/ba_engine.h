@@ -25,6 +25,9 @@ void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason);
 void ba_set_robust(vo_ctx* ctx, double huber_delta);
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
 int ba_covariance(vo_ctx* ctx, double lambda, double* pose_cov, double* pose_dense, double* point_cov);
+void ba_set_obs_weights(vo_ctx* ctx, const double* w);
+void ba_get_obs_weights(vo_ctx* ctx, double* w_out);
+void ba_cull(vo_ctx* ctx, const vo_ba_cull_options* opt, int32_t* n_culled, int32_t* n_active, bool sync);
 int ba_stats(vo_ctx* ctx, int64_t* out, int n);
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n);
 int ba_chain_stamps(vo_ctx* ctx, uint64_t* out, int n);

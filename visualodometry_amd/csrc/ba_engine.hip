@@ -16,6 +16,7 @@
 #include "ba_cov.h"
 #include "ba_kernels.h"
 #include "ba_plan.h"
+#include "ba_weights.h"
 #include "vo_ctx.h"
 
 #ifndef VO_BA_CHAIN
@@ -183,6 +184,8 @@ class BAEngine {
     lm_stop_ = vo_ba_lm_stop{};  // and with an LM loop that never stops early
     obs_uploaded_ = false;
     cov_uploaded_ = false;
+    weighted_ = false;  // every observation at weight 1: the kernels of a session without weights
+    wt_tables_ = false;
     session_ = ++g_ba_sessions;
     return session_;
   }
@@ -336,6 +339,7 @@ class BAEngine {
     require_state();
     VO_REQUIRE(std::isfinite(lambda) && lambda >= 0.0, VO_ERR_ARG, "vo_ba_covariance: lambda must be finite and >= 0");
     VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_covariance: not with a communicator of more than one rank");
+    require_weighted_layout("vo_ba_covariance");
     const BAPlan& P = plan_;
     const int F = P.n_free, L = P.n_points;
     const size_t n = 6ull * F;
@@ -354,8 +358,7 @@ class BAEngine {
         A.lm_lambda = nullptr;
         A.status = nullptr;
         A.nseg = P.n_segments();
-        const bool wave = plan_is_wave(P.seg_obs);
-        launch_lin(A, huber_ > 0.0 ? kAccum | kRobust : kAccum, wave ? P.seg_chunks : 0, A.nseg, st);
+        launch_k1(A, kAccum, plan_is_wave(P.seg_obs) ? P.seg_chunks : 0, "vo_ba_covariance");
         VO_HIP_CHECK(hipGetLastError());
       } else {
         VO_HIP_CHECK(hipMemsetAsync(d_slab_cost_.ptr, 0, 8, st));
@@ -410,6 +413,7 @@ class BAEngine {
       Q.poses = d_pose_[cur_].as<double>();
       Q.points = d_points_.as<double>();
       Q.cov = d_cov_.as<double>();
+      Q.sqrt_w = weighted_ ? d_sqw_obs_.as<double>() : nullptr;
       Q.out = d_cov_pts_.as<double>();
       launch_cov_points(Q, st);
       VO_HIP_CHECK(hipGetLastError());
@@ -441,7 +445,11 @@ class BAEngine {
     const BAPlan& P = plan_;
     hipStream_t st = ctx_->stream;
     const size_t M = (size_t)P.n_obs;
-    std::vector<int32_t> ptr(P.n_points + 1, 0), inv(std::max(1, P.n_points), 0);
+    // (host sources that live as long as the session: the copies need no synchronisation, and the
+    // vectors are rewritten only behind the next setup's)
+    std::vector<int32_t>&ptr = h_cov_ptr_, &inv = h_cov_inv_;
+    ptr.assign(P.n_points + 1, 0);
+    inv.assign(std::max(1, P.n_points), 0);
     for (int q = 0; q < P.n_points; ++q) inv[P.pt_perm[q]] = q;
     for (size_t pos = 0; pos < M; ++pos) ++ptr[P.pt_perm[P.te_pt[P.obs_te[pos]]] + 1];
     for (int p = 0; p < P.n_points; ++p) ptr[p + 1] += ptr[p];
@@ -452,7 +460,6 @@ class BAEngine {
     upload(d_cov_last_, P.prof_last, st);
     upload(d_cov_dst_, red_dst_, st);
     d_cov_fail_.reserve(sizeof(int));
-    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
     cov_uploaded_ = true;
   }
 
@@ -463,9 +470,13 @@ class BAEngine {
     const BAPlan& P = plan_;
     hipStream_t st = ctx_->stream;
     const size_t M = (size_t)P.n_obs;
-    std::vector<int32_t> cam(M), pt(M);
-    std::vector<float> uv(2 * M);
     VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "BA read-out: the plan has no observation order");
+    // (session-long host sources, as upload_cov_tables')
+    std::vector<int32_t>&cam = h_obs_cam_, &pt = h_obs_pt_;
+    std::vector<float>& uv = h_obs_uv_;
+    cam.resize(M);
+    pt.resize(M);
+    uv.resize(2 * M);
     for (size_t pos = 0; pos < M; ++pos) {  // internal position -> problem observation (ba_plan.h)
       const size_t o = (size_t)P.obs_order[pos];
       cam[o] = P.obs_cam[pos];
@@ -476,14 +487,125 @@ class BAEngine {
     upload(d_obs_cam_, cam, st);
     upload(d_obs_pt_, pt, st);
     upload(d_obs_uv_, uv, st);
-    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
     obs_uploaded_ = true;
+  }
+
+  // vo_ba_set_obs_weights: information weights in problem order, null for all ones (the session
+  // then has no weights again).  sqrt(w) is taken here, in IEEE double; the device only multiplies.
+  void set_obs_weights(const double* w) {
+    VO_REQUIRE(have_problem_, VO_ERR_STATE, "vo_ba_set_obs_weights before vo_ba_setup");
+    VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_set_obs_weights: not with a communicator of more than one rank");
+    const BAPlan& P = plan_;
+    const size_t M = (size_t)P.n_obs;
+    if (w)
+      for (size_t o = 0; o < M; ++o)
+        VO_REQUIRE(std::isfinite(w[o]) && w[o] >= 0.0, VO_ERR_ARG,
+                   "vo_ba_set_obs_weights: weight %zu is negative or not finite", o);
+    apply_pending();  // under the weights the step was solved with
+    if (!w) {
+      weighted_ = false;
+      return;
+    }
+    upload_weight_tables();
+    hipStream_t st = ctx_->stream;
+    std::vector<double> ww(w, w + M), so(M), sp(M);
+    for (size_t o = 0; o < M; ++o) so[o] = std::sqrt(w[o]);
+    for (size_t pos = 0; pos < M; ++pos) sp[pos] = so[(size_t)P.obs_order[pos]];
+    upload(d_w_, ww, st);
+    upload(d_sqw_obs_, so, st);
+    upload(d_sqw_plan_, sp, st);
+    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
+    weighted_ = true;
+  }
+
+  // vo_ba_get_obs_weights: synchronises; what was set, the culled observations at 0.
+  void get_obs_weights(double* w_out) {
+    VO_REQUIRE(have_problem_, VO_ERR_STATE, "vo_ba_get_obs_weights before vo_ba_setup");
+    VO_REQUIRE(w_out, VO_ERR_ARG, "vo_ba_get_obs_weights: null output");
+    const size_t M = (size_t)plan_.n_obs;
+    hipStream_t st = ctx_->stream;
+    if (weighted_ && M) VO_HIP_CHECK(hipMemcpyAsync(w_out, d_w_.ptr, M * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    if (!weighted_) std::fill(w_out, w_out + M, 1.0);
+  }
+
+  // vo_ba_cull / _async (vo_hip.h): two kernels on the stream at the device state, nothing but the
+  // weight arrays and the counters written.  From here on the session has weights (a synchronous
+  // cull of a session without them that culled nothing leaves it without).
+  void cull(const vo_ba_cull_options* opt, int32_t* n_culled_out, int32_t* n_active_out, bool sync) {
+    const char* who = sync ? "vo_ba_cull" : "vo_ba_cull_async";
+    VO_REQUIRE(opt, VO_ERR_ARG, "%s: null options", who);
+    VO_REQUIRE(std::isfinite(opt->max_chi2) && std::isfinite(opt->min_depth), VO_ERR_ARG, "%s: non-finite option", who);
+    VO_REQUIRE(opt->max_chi2 >= 0.0, VO_ERR_ARG, "%s: max_chi2 < 0", who);
+    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "%s: reserved must be 0", who);
+    require_state();
+    VO_REQUIRE(!sharded(), VO_ERR_STATE, "%s: not with a communicator of more than one rank", who);
+    apply_pending();
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const int M = P.n_obs;
+    upload_cov_tables();  // the problem-order observation arrays and CSR
+    upload_weight_tables();
+    const bool was_weighted = weighted_;
+    if (!weighted_) {
+      launch_fill(d_w_.as<double>(), M, 1.0, st);
+      launch_fill(d_sqw_obs_.as<double>(), M, 1.0, st);
+      launch_fill(d_sqw_plan_.as<double>(), M, 1.0, st);
+      VO_HIP_CHECK(hipGetLastError());
+      weighted_ = true;
+    }
+    VO_HIP_CHECK(hipMemsetAsync(d_cull_cnt_.ptr, 0, 2 * sizeof(int), st));
+    CullArgs C;
+    C.n_obs = M;
+    C.n_points = P.n_points;
+    C.min_track = opt->min_track;
+    C.fx = prob_.fx; C.fy = prob_.fy; C.cx = prob_.cx; C.cy = prob_.cy;
+    C.max_chi2 = opt->max_chi2;
+    C.min_depth = opt->min_depth;
+    C.obs_cam = d_obs_cam_.as<int>();
+    C.obs_pt = d_obs_pt_.as<int>();
+    C.obs_uv = d_obs_uv_.as<float2>();
+    C.obs_pos = d_obs_pos_.as<int>();
+    C.point_ptr = d_cov_ptr_.as<int>();
+    C.poses = d_pose_[cur_].as<double>();
+    C.points = d_points_.as<double>();
+    C.w = d_w_.as<double>();
+    C.sqw_obs = d_sqw_obs_.as<double>();
+    C.sqw_plan = d_sqw_plan_.as<double>();
+    C.count = d_cull_cnt_.as<int>();
+    launch_cull(C, st);
+    VO_HIP_CHECK(hipGetLastError());
+    if (!sync) return;
+    int cnt[2] = {0, 0};
+    VO_HIP_CHECK(hipMemcpyAsync(cnt, d_cull_cnt_.ptr, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    if (n_culled_out) *n_culled_out = cnt[0];
+    if (n_active_out) *n_active_out = cnt[1];
+    if (!was_weighted && cnt[0] == 0) weighted_ = false;  // still all ones
+  }
+
+  // The weight arrays and the problem observation -> plan position map, on a session's first use.
+  void upload_weight_tables() {
+    if (wt_tables_) return;
+    const BAPlan& P = plan_;
+    const size_t M = (size_t)P.n_obs;
+    VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "BA weights: the plan has no observation order");
+    std::vector<int32_t>& pos_of = h_obs_pos_;  // (a session-long host source: no synchronisation)
+    pos_of.assign(std::max<size_t>(M, 1), 0);
+    for (size_t pos = 0; pos < M; ++pos) pos_of[(size_t)P.obs_order[pos]] = (int32_t)pos;
+    upload(d_obs_pos_, pos_of, ctx_->stream);
+    d_w_.reserve(std::max<size_t>(M, 1) * 8);
+    d_sqw_obs_.reserve(std::max<size_t>(M, 1) * 8);
+    d_sqw_plan_.reserve(std::max<size_t>(M, 1) * 8);
+    d_cull_cnt_.reserve(2 * sizeof(int));
+    wt_tables_ = true;
   }
 
   // iters GN iterations; sync=true finalises and reads the costs back.
   int run(int iters, double* cost_out, bool sync) {
     require_state();
     VO_REQUIRE(iters >= 0, VO_ERR_ARG, "vo_ba_run: iters < 0");
+    require_weighted_layout("vo_ba_run");
     hipStream_t st = ctx_->stream;
     d_cost_.reserve((iters + 1) * 8ull);
     // Chained (chain_ok): a stand-alone K1, then iters - 1 solve launches that each carry the next
@@ -525,6 +647,7 @@ class BAEngine {
     require_state();
     VO_REQUIRE(iters >= 0, VO_ERR_ARG, "vo_ba_run_lm: iters < 0");
     VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_run_lm: not with a communicator of more than one rank");
+    require_weighted_layout("vo_ba_run_lm");
     const vo_ba_lm_options o = lm_options(opt);
     hipStream_t st = ctx_->stream;
     apply_pending();  // a pending GN step: under the lambda and delta it was solved with
@@ -698,6 +821,7 @@ class BAEngine {
 
   int gn_step(double* S_out, double* b_out, double* dc_out, double* cost_out) {
     require_state();
+    require_weighted_layout("vo_ba_gn_step");
     hipStream_t st = ctx_->stream;
     const BAPlan& P = plan_;
     const int F = P.n_free;
@@ -1103,9 +1227,39 @@ class BAEngine {
     }
     // inside an LM run (lm_lambda_ set) the modes that use the damping read it from the device
     if (lm_lambda_ && mode != 0) mode |= kLm;
-    launch_lin(A, huber_ > 0.0 ? mode | kRobust : mode, wave ? nw : 0, nseg, ctx_->stream);
+    launch_k1(A, mode, wave ? nw : 0, "BA");
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
+  }
+
+  // A session with observation weights on a K1 layout without a weighted form: refused before
+  // anything is enqueued or any run state is touched.
+  void require_weighted_layout(const char* who) const {
+    if (!weighted_ || plan_.n_segments() <= 0) return;
+    const int nw = plan_is_wave(plan_.seg_obs) ? plan_.seg_chunks : 0;
+    VO_REQUIRE(lin_weighted_covers(nw), VO_ERR_STATE,
+               "%s: the session has observation weights, and its K1 layout (%s) has no weighted instantiation", who,
+               nw ? "one-wave, too many chunks per segment" : "four-wave");
+  }
+
+  // K1 of one mode (kBacksub | kAccum | kLm) on the context stream: the Huber instantiations under
+  // a robust cost, and for a session with observation weights the weighted ones (ba_weights.hip),
+  // which exist for the one-wave K1 only -- any other layout refuses the run, it never drops the
+  // weights.
+  void launch_k1(LinArgs& A, int mode, int wave_chunks, const char* who) {
+    if (!weighted_) {
+      launch_lin(A, huber_ > 0.0 ? mode | kRobust : mode, wave_chunks, A.nseg, ctx_->stream);
+      return;
+    }
+    if (!(huber_ > 0.0)) {
+      A.huber = kWeightedNoHuber;
+      A.huber2 = kWeightedNoHuber * kWeightedNoHuber;
+    }
+    const bool ok = launch_lin_weighted(A, d_sqw_plan_.as<double>(), mode, wave_chunks, A.nseg, ctx_->stream);
+    VO_REQUIRE(ok, VO_ERR_STATE,
+               "%s: the session has observation weights, and this K1 layout (chunks per segment %d, mode %d) has no "
+               "weighted instantiation",
+               who, wave_chunks, mode);
   }
 
   // K2 runs inside the banded K3's launch (one rank: no all-reduce between them)
@@ -1258,6 +1412,7 @@ class BAEngine {
     return VO_BA_CHAIN && !ctx_->ba_no_chain && band_on_ && fused() && band_lds_.full && !band_lds_.split &&
            plan_is_wave(plan_.seg_obs) && plan_.seg_chunks == kBandChainChunks && nseg > 0 &&
            (int64_t)nseg * kBandChainChunks == plan_.n_chunks() && nseg + 2 <= ctx_->num_cus && !lm_lambda_ &&
+           !weighted_ &&  // observation weights: the separate K1 launch (the chained K1 has no weighted form)
            !ctx_->prof.on && (!stamps_on_ || ctx_->ba_chain_stamps) && !sharded();
   }
 
@@ -1397,6 +1552,15 @@ class BAEngine {
   bool cov_uploaded_ = false;
   DevBuf d_cov_ptr_, d_cov_inv_, d_cov_first_, d_cov_off_, d_cov_last_, d_cov_dst_;
   DevBuf d_cov_l_, d_cov_, d_cov_pts_, d_cov_fail_;
+  // observation weights (set_obs_weights, cull): whether the session has any (false: every launch
+  // is the unweighted one), w and sqrt(w) in problem order, sqrt(w) in the plan's order (K1), the
+  // problem observation -> plan position map and the cull's two counters
+  bool weighted_ = false, wt_tables_ = false;
+  DevBuf d_w_, d_sqw_obs_, d_sqw_plan_, d_obs_pos_, d_cull_cnt_;
+  // host sources of the read-outs' and the cull's tables (upload_obs, upload_cov_tables,
+  // upload_weight_tables): kept for the session, so their copies need no synchronisation
+  std::vector<int32_t> h_obs_cam_, h_obs_pt_, h_cov_ptr_, h_cov_inv_, h_obs_pos_;
+  std::vector<float> h_obs_uv_;
 };
 
 // ---- entry points used by api.hip -------------------------------------------------
@@ -1430,6 +1594,11 @@ void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }
 int ba_covariance(vo_ctx* ctx, double lambda, double* pose_cov, double* pose_dense, double* point_cov) {
   return ba_engine(ctx)->covariance(lambda, pose_cov, pose_dense, point_cov);
+}
+void ba_set_obs_weights(vo_ctx* ctx, const double* w) { ba_engine(ctx)->set_obs_weights(w); }
+void ba_get_obs_weights(vo_ctx* ctx, double* w_out) { ba_engine(ctx)->get_obs_weights(w_out); }
+void ba_cull(vo_ctx* ctx, const vo_ba_cull_options* opt, int32_t* n_culled, int32_t* n_active, bool sync) {
+  ba_engine(ctx)->cull(opt, n_culled, n_active, sync);
 }
 int ba_stats(vo_ctx* ctx, int64_t* out, int n) { return ba_engine(ctx)->stats(out, n); }
 int ba_stamps(vo_ctx* ctx, uint64_t* out, int n) { return ba_engine(ctx)->read_stamps(out, n); }

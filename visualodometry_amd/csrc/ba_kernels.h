@@ -26,7 +26,11 @@ constexpr int kS3Count = 10;  // values of the profile K3's stamp row (ba.hip kS
 // kLm (Levenberg-Marquardt step control, vo_ba_run_lm): the damping is read from the device
 // (LinArgs::lm_lambda) instead of LinArgs::lambda; instantiated for the two modes the LM loop
 // needs it in, kAccum and kBacksub alone (the cost-only kernel uses no damping), plain and kRobust.
-enum { kBacksub = 1, kAccum = 2, kRobust = 4, kLm = 8 };
+// kWeighted (per-observation weights, vo_ba_set_obs_weights / vo_ba_cull): the one-wave K1 reads
+// sqrt(w) per observation; instantiated in ba_weights.hip for the modes a weighted session
+// launches, always with kRobust (a session without Huber runs that code under a delta no whitened
+// residual reaches), so the kernels above keep their code and their arguments.
+enum { kBacksub = 1, kAccum = 2, kRobust = 4, kLm = 8, kWeighted = 16 };
 
 struct LinArgs {
   int n_fixed;

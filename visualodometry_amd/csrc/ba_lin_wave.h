@@ -141,9 +141,12 @@ __device__ __forceinline__ bool point_block_w(const LinWave& S, double lambda, i
 // r and Jp into the Zb region, Jc (kJc) into S.Jc.  The back substitution (kBack) adds
 // Jc dc for a free camera (dc non-null) and sums no cost.  kRob: as lin_obs / chunk_backsub -- the
 // Huber scale of the raw residual (before Jc dc) on r and the Jacobians, the cost sums rho.
-template <bool kJc, bool kBack, bool kRob>
+// kWt (observation weights, DESIGN.md §Observation weights and culling): sw = sqrt(w_o) multiplies
+// r and the Jacobians ahead of the Huber rule, which then sees the whitened residual; sw == 0 is a
+// select, not a product, so an inactive observation with a non-finite raw residual leaves zeros.
+template <bool kJc, bool kBack, bool kRob, bool kWt = false>
 __device__ __forceinline__ void obs_lin_w(LinWave& S, const LinArgs& A, const double* T, int o,
-                                          const double* dc, double& cost) {
+                                          const double* dc, double& cost, double sw = 1.0) {
   const int q = S.img.obs_pt[o];
   const double X0 = S.X[q][0], X1 = S.X[q][1], X2 = S.X[q][2];
   const double x = T[0] * X0 + T[1] * X1 + T[2] * X2 + T[9];
@@ -155,6 +158,12 @@ __device__ __forceinline__ void obs_lin_w(LinWave& S, const LinArgs& A, const do
   double r1 = A.fy * y * iz + A.cy - (double)m.y;
   double j00 = A.fx * iz, j02 = -A.fx * x * iz * iz;
   double j11 = A.fy * iz, j12 = -A.fy * y * iz * iz;
+  if constexpr (kWt) {
+    const bool on = sw > 0.0;
+    r0 = on ? r0 * sw : 0.0; r1 = on ? r1 * sw : 0.0;
+    j00 = on ? j00 * sw : 0.0; j02 = on ? j02 * sw : 0.0;
+    j11 = on ? j11 * sw : 0.0; j12 = on ? j12 * sw : 0.0;
+  }
   if constexpr (kRob) {
     double rho;
     const double s = huber_scale(r0, r1, A.huber, A.huber2, rho);
@@ -426,11 +435,16 @@ __device__ __forceinline__ double ld_sc1_f64(const double* p) {
 // seg: its segment.  kGated: see LinGate -- level 1 and the level-2 loads that do not depend on
 // the solve (landmarks, pose_old, slab rows) and their LDS stores come before the gate, pose_new
 // and dc behind it by sc1 loads only, and the body from the back substitution on is the same code.
+// kWeighted modes: sqw holds sqrt(w) per observation in the plan's observation order (the chunk's
+// first at header int 0); every other mode neither reads nor receives it.
 template <int MODE, bool kStamp, int NW, bool kGated>
-__device__ __forceinline__ void lin_wave_body(LinArgs A, LinWave* Sw, int* s_arrive_p, const int seg, const LinGate G) {
+__device__ __forceinline__ void lin_wave_body(LinArgs A, LinWave* Sw, int* s_arrive_p, const int seg, const LinGate G,
+                                              const double* sqw = nullptr) {
   int& s_arrive = *s_arrive_p;
   constexpr bool kGroup = NW > 1;
   constexpr bool kRob = (MODE & kRobust) != 0;
+  constexpr bool kWt = (MODE & kWeighted) != 0;
+  static_assert(!kWt || (kRob && !kGated), "weighted K1: the Huber code, never in the chained launch");
   if constexpr ((MODE & kLm) != 0) A.lambda = *A.lm_lambda;  // step control: the damping is on the device
   // the cross-chunk combine: its waves, whether they start before the late waves are done, and
   // a thread's 16-byte pieces of the slots' blocks and of the rhs
@@ -503,6 +517,8 @@ __device__ __forceinline__ void lin_wave_body(LinArgs A, LinWave* Sw, int* s_arr
       if (!kGated) vdc[k] = A.dc[6l * i_wcam[k] + e % 6];
     }
   }
+  double sw = 1.0;
+  if constexpr (kWt) sw = sqw[nob > 0 ? h0.x + min(tid, nob - 1) : 0];  // (a padding chunk: any entry)
   int vsp = 0, vcp = 0;
   if ((MODE & kAccum) && nslots > 0) {
     vsp = A.slab_pos[slot_off + min(tid, nslots - 1)];
@@ -596,7 +612,8 @@ __device__ __forceinline__ void lin_wave_body(LinArgs A, LinWave* Sw, int* s_arr
     // dp = -V^-1 sum Jp^T (r + Jc dc) per landmark (chunk_backsub)
     if (tid < nob) {
       const int lc = S.img.obs_lcam[tid];
-      obs_lin_w<false, true, kRob>(S, A, &pose_o[12 * S.img.acam[tid]], tid, lc >= 0 ? &dcw[6 * lc] : nullptr, cost);
+      obs_lin_w<false, true, kRob, kWt>(S, A, &pose_o[12 * S.img.acam[tid]], tid, lc >= 0 ? &dcw[6 * lc] : nullptr, cost,
+                                        sw);
     }
     lds_sync_wave();
     if (tid < npt) {
@@ -618,7 +635,8 @@ __device__ __forceinline__ void lin_wave_body(LinArgs A, LinWave* Sw, int* s_arr
   }
 
   // residuals and Jacobians at the current linearisation point (cost at the updated state)
-  if (tid < nob) obs_lin_w<(MODE & kAccum) != 0, false, kRob>(S, A, S.pose_n[S.img.acam[tid]], tid, nullptr, cost);
+  if (tid < nob)
+    obs_lin_w<(MODE & kAccum) != 0, false, kRob, kWt>(S, A, S.pose_n[S.img.acam[tid]], tid, nullptr, cost, sw);
   if (MODE & kAccum) {
     lds_sync_wave();
     st.mark(kPhLinObs);

@@ -56,6 +56,10 @@ class VOConfig:
     ba_lm_xtol: float = 0.0  # stop once an accepted step's largest pose-update entry is at most this
     ba_lm_max_rejects: int = 0  # stop after this many rejected steps in a row
     ba_covariance: bool = False  # also read out the pose and landmark covariance of each adjusted window
+    # device-side outlier culling: ba_cull_rounds = R > 0 runs R + 1 solves of ba_iters with a cull between them
+    ba_cull_rounds: int = 0  # 0: off
+    ba_cull_chi2: float = 0.0  # deactivate an observation whose weighted squared error (px^2) exceeds this; 0: not tested
+    ba_cull_min_depth: float = 0.0  # deactivate an observation at or below this camera-frame depth
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)

@@ -140,13 +140,20 @@ class KeyframeWindow:
                      obs_pt=remap[inv].astype(np.int32), n_fixed=self.n_fixed)
         return w, lm_ids
 
-    def write_back(self, res: BAResult, lm_ids, map_points: dict) -> None:
+    def write_back(self, res: BAResult, lm_ids, map_points: dict, obs_pt=None) -> None:
+        """``obs_pt``: the window's landmark per observation, needed only under culling
+        (``res.obs_active``)."""
         for fr, P in zip(self.frames, res.poses_cw):
             fr.T_wc = np.linalg.inv(P)
+        lm_ids, points = np.asarray(lm_ids), np.asarray(res.points)
+        if res.obs_active is not None and obs_pt is not None:
+            # culling: a landmark all of whose observations were culled was held by nothing
+            live = np.bincount(np.asarray(obs_pt)[res.obs_active], minlength=lm_ids.size) > 0
+            lm_ids, points = lm_ids[live], points[live]
         if isinstance(map_points, MapStore):
-            map_points.scatter(lm_ids, res.points)
+            map_points.scatter(lm_ids, points)
             return
-        for i, X in zip(lm_ids, res.points):
+        for i, X in zip(lm_ids, points):
             old = map_points[int(i)]
             map_points[int(i)] = np.asarray(X, dtype=np.asarray(old).dtype).reshape(np.shape(old))
 
@@ -199,7 +206,7 @@ def run_window_ba(vo, win: KeyframeWindow):
             res.cost_per_iter[-1] > res.cost_per_iter[0]:
         print(f"BA: window rejected ({res.status} {res.message})")
         return res
-    win.write_back(res, lm_ids, vo.map_points)
+    win.write_back(res, lm_ids, vo.map_points, window.obs_pt)
     T_wc = win.frames[-1].T_wc.copy()
     vo.T_wc = T_wc
     vo.keyframe["T_wc"] = T_wc.copy()
