@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <array>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "ba_band.h"
@@ -180,6 +181,22 @@ void match_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n
 }  // namespace vo
 
 using vo::guarded;
+
+// A vo_ba_* call on a session: bind, the caller's argument check (arg_error: its message, null if
+// the arguments are fine), the session check, then f, whose return code (if it has one) is the
+// call's unless something threw.
+template <class F>
+static int ba_call(vo_ctx* ctx, uint64_t session, F&& f, const char* arg_error = nullptr) {
+  int rc = VO_OK;
+  const int g = guarded([&] {
+    vo::bind(ctx);
+    VO_REQUIRE(!arg_error, VO_ERR_ARG, "%s", arg_error);
+    vo::ba_check_session(ctx, session);
+    if constexpr (std::is_void_v<decltype(f())>) f();
+    else rc = f();
+  });
+  return g != VO_OK ? g : rc;
+}
 
 extern "C" {
 
@@ -699,157 +716,81 @@ int vo_ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_f
 }
 
 int vo_ba_set_state(vo_ctx* ctx, uint64_t session, const double* poses, const double* points) {
-  return guarded([&] {
-    vo::bind(ctx);
-    VO_REQUIRE(poses && points, VO_ERR_ARG, "vo_ba_set_state: null arrays");
-    vo::ba_check_session(ctx, session);
-    vo::ba_set_state(ctx, poses, points);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_set_state(ctx, poses, points); },
+                 poses && points ? nullptr : "vo_ba_set_state: null arrays");
 }
 
 int vo_ba_get_state(vo_ctx* ctx, uint64_t session, double* poses, double* points) {
-  return guarded([&] {
-    vo::bind(ctx);
-    VO_REQUIRE(poses && points, VO_ERR_ARG, "vo_ba_get_state: null arrays");
-    vo::ba_check_session(ctx, session);
-    vo::ba_get_state(ctx, poses, points);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_get_state(ctx, poses, points); },
+                 poses && points ? nullptr : "vo_ba_get_state: null arrays");
 }
 
 int vo_ba_run(vo_ctx* ctx, uint64_t session, int iters, double* cost_out) {
-  int rc = VO_OK;
-  int g = guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    rc = vo::ba_run(ctx, iters, cost_out, true);
-  });
-  return g != VO_OK ? g : rc;
+  return ba_call(ctx, session, [&] { return vo::ba_run(ctx, iters, cost_out, true); });
 }
 
 int vo_ba_run_async(vo_ctx* ctx, uint64_t session, int iters) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_run(ctx, iters, nullptr, false);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_run(ctx, iters, nullptr, false); });
 }
 
 int vo_ba_gn_step(vo_ctx* ctx, uint64_t session, double* S_out, double* b_out, double* dc_out,
                   double* cost_out) {
-  int rc = VO_OK;
-  int g = guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    rc = vo::ba_gn_step(ctx, S_out, b_out, dc_out, cost_out);
-  });
-  return g != VO_OK ? g : rc;
+  return ba_call(ctx, session, [&] { return vo::ba_gn_step(ctx, S_out, b_out, dc_out, cost_out); });
 }
 
 int vo_ba_run_lm(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_options* opt, double* cost_out,
                  double* lambda_out, double* trial_out, uint8_t* accepted_out) {
-  int rc = VO_OK;
-  int g = guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    rc = vo::ba_run_lm(ctx, iters, opt, cost_out, lambda_out, trial_out, accepted_out, true);
-  });
-  return g != VO_OK ? g : rc;
+  return ba_call(ctx, session,
+                 [&] { return vo::ba_run_lm(ctx, iters, opt, cost_out, lambda_out, trial_out, accepted_out, true); });
 }
 
 int vo_ba_run_lm_async(vo_ctx* ctx, uint64_t session, int iters, const vo_ba_lm_options* opt) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_run_lm(ctx, iters, opt, nullptr, nullptr, nullptr, nullptr, false);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_run_lm(ctx, iters, opt, nullptr, nullptr, nullptr, nullptr, false); });
 }
 
 int vo_ba_lm_log(vo_ctx* ctx, uint64_t session, int n, double* cost_out, double* lambda_out, double* trial_out,
                  uint8_t* accepted_out) {
-  int rc = VO_OK;
-  int g = guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    rc = vo::ba_lm_log(ctx, n, cost_out, lambda_out, trial_out, accepted_out);
-  });
-  return g != VO_OK ? g : rc;
+  return ba_call(ctx, session, [&] { return vo::ba_lm_log(ctx, n, cost_out, lambda_out, trial_out, accepted_out); });
 }
 
 int vo_ba_set_lm_stop(vo_ctx* ctx, uint64_t session, const vo_ba_lm_stop* stop) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_set_lm_stop(ctx, stop);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_set_lm_stop(ctx, stop); });
 }
 
 int vo_ba_lm_stop_info(vo_ctx* ctx, uint64_t session, int32_t* trials_out, int32_t* reason_out) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_lm_stop_info(ctx, trials_out, reason_out);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_lm_stop_info(ctx, trials_out, reason_out); });
 }
 
 int vo_ba_set_robust(vo_ctx* ctx, uint64_t session, double huber_delta) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_set_robust(ctx, huber_delta);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_set_robust(ctx, huber_delta); });
 }
 
 int vo_ba_residuals(vo_ctx* ctx, uint64_t session, double* err2_out, double* depth_out) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_residuals(ctx, err2_out, depth_out);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_residuals(ctx, err2_out, depth_out); });
 }
 
 int vo_ba_covariance(vo_ctx* ctx, uint64_t session, double lambda, double* pose_cov_out, double* pose_dense_out,
                      double* point_cov_out) {
-  int rc = VO_OK;
-  int g = guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    rc = vo::ba_covariance(ctx, lambda, pose_cov_out, pose_dense_out, point_cov_out);
-  });
-  return g != VO_OK ? g : rc;
+  return ba_call(ctx, session,
+                 [&] { return vo::ba_covariance(ctx, lambda, pose_cov_out, pose_dense_out, point_cov_out); });
 }
 
 int vo_ba_set_obs_weights(vo_ctx* ctx, uint64_t session, const double* w) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_set_obs_weights(ctx, w);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_set_obs_weights(ctx, w); });
 }
 
 int vo_ba_get_obs_weights(vo_ctx* ctx, uint64_t session, double* w_out) {
-  return guarded([&] {
-    vo::bind(ctx);
-    VO_REQUIRE(w_out, VO_ERR_ARG, "vo_ba_get_obs_weights: null output");
-    vo::ba_check_session(ctx, session);
-    vo::ba_get_obs_weights(ctx, w_out);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_get_obs_weights(ctx, w_out); },
+                 w_out ? nullptr : "vo_ba_get_obs_weights: null output");
 }
 
 int vo_ba_cull(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt, int32_t* n_culled_out,
                int32_t* n_active_out) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_cull(ctx, opt, n_culled_out, n_active_out, true);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_cull(ctx, opt, n_culled_out, n_active_out, true); });
 }
 
 int vo_ba_cull_async(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt) {
-  return guarded([&] {
-    vo::bind(ctx);
-    vo::ba_check_session(ctx, session);
-    vo::ba_cull(ctx, opt, nullptr, nullptr, false);
-  });
+  return ba_call(ctx, session, [&] { vo::ba_cull(ctx, opt, nullptr, nullptr, false); });
 }
 
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points, int iters,

@@ -16,6 +16,7 @@
 #include "ba_cov.h"
 #include "ba_kernels.h"
 #include "ba_plan.h"
+#include "ba_tables.h"
 #include "ba_weights.h"
 #include "vo_ctx.h"
 
@@ -88,6 +89,8 @@ struct TablePack {
 };
 
 std::atomic<uint64_t> g_ba_sessions{0};  // session ids, unique in the process
+
+static_assert(kTabTranspose == kRedTranspose, "ba_tables.h restates K2's transpose flag");
 
 }  // namespace
 
@@ -164,6 +167,9 @@ class BAEngine {
                  "vo_ba_setup: %d free poses / panel of %d blocks exceed the solver's LDS budget", F,
                  TL.max_panel);
       solve_lds_size_ = solve_layout_.total;
+      solve_max_panel_ = std::max(1, TL.max_panel);
+      solve_max_row_span_ = 0;
+      for (int k = 0; k < F; ++k) solve_max_row_span_ = std::max(solve_max_row_span_, k - P.prof_first[k]);
     }
     PLAN_T(9, "setup: bufs");
     reduce_tables(pack);
@@ -179,13 +185,7 @@ class BAEngine {
     have_state_ = false;
     pending_ = false;
     cur_ = 0;
-    huber_ = 0.0;  // every problem starts with the plain cost
-    lm_iters_ = -1;  // without an LM log
-    lm_stop_ = vo_ba_lm_stop{};  // and with an LM loop that never stops early
-    obs_uploaded_ = false;
-    cov_uploaded_ = false;
-    weighted_ = false;  // every observation at weight 1: the kernels of a session without weights
-    wt_tables_ = false;
+    sess_ = Session{};  // nothing of the previous problem's settings, lazy tables or LM run
     session_ = ++g_ba_sessions;
     return session_;
   }
@@ -204,16 +204,8 @@ class BAEngine {
                VO_ERR_ARG, "vo_ba_reserve: bad sizes");
     VO_REQUIRE(!sharded(), VO_ERR_STATE,
                "vo_ba_reserve: before vo_comm_init (a setup with a communicator is collective)");
-    const int len0 = (int)std::min<int64_t>(n_poses, n_obs / n_points);
-    const int64_t extra = std::min<int64_t>(n_obs - (int64_t)len0 * n_points, n_points);
-    std::vector<int32_t> ptr(n_points + 1), cam;
-    cam.reserve(n_obs);
-    for (int p = 0; p < n_points; ++p) {
-      const int len = std::min(n_poses, len0 + (p < extra ? 1 : 0));
-      const int c0 = (int)((int64_t)p * (n_poses - len + 1) / n_points);
-      for (int c = 0; c < len; ++c) cam.push_back(c0 + c);
-      ptr[p + 1] = (int32_t)cam.size();
-    }
+    const ReserveWindow W = reserve_window(n_poses, n_points, n_obs);
+    const std::vector<int32_t>&ptr = W.point_ptr, &cam = W.obs_cam;
     std::vector<float> uv(2 * cam.size(), 0.0f);
     vo_ba_problem pr{};
     pr.n_poses = n_poses;
@@ -230,7 +222,7 @@ class BAEngine {
     d_cost_.reserve(64 * 8);
     // step control (run_lm): the landmark snapshot and a log of up to 64 iterations
     d_lm_snap_.reserve(24ull * n_points);
-    d_lm_log_.reserve(lm_log_bytes(64));
+    d_lm_log_.reserve(LmLog{64}.bytes());
     VO_HIP_CHECK(hipStreamSynchronize(ctx_->stream));
     plan_ok_ = false;  // nothing of the synthetic plan is taken over
     have_problem_ = false;
@@ -294,9 +286,9 @@ class BAEngine {
   void set_robust(double delta) {
     VO_REQUIRE(have_problem_, VO_ERR_STATE, "vo_ba_set_robust before vo_ba_setup");
     VO_REQUIRE(std::isfinite(delta) && delta >= 0.0, VO_ERR_ARG, "vo_ba_set_robust: huber_delta must be finite and >= 0");
-    if (delta == huber_) return;
+    if (delta == sess_.huber) return;
     apply_pending();
-    huber_ = delta;
+    sess_.huber = delta;
   }
 
   // Raw squared reprojection error and camera-frame depth of every observation, in the order of
@@ -352,16 +344,13 @@ class BAEngine {
     if (F > 0) {
       // the system: enqueue_lin / enqueue_reduce without their profiler brackets, status tests and
       // LM damping
-      if (P.n_segments() > 0) {
-        LinArgs A = lin_args();
-        A.lambda = lambda;
-        A.lm_lambda = nullptr;
-        A.status = nullptr;
-        A.nseg = P.n_segments();
-        launch_k1(A, kAccum, plan_is_wave(P.seg_obs) ? P.seg_chunks : 0, "vo_ba_covariance");
+      K1Launch k1;
+      if (prepare_k1(k1)) {
+        k1.A.lambda = lambda;
+        k1.A.lm_lambda = nullptr;
+        k1.A.status = nullptr;
+        launch_k1(k1.A, kAccum, k1.wave_chunks, "vo_ba_covariance");
         VO_HIP_CHECK(hipGetLastError());
-      } else {
-        VO_HIP_CHECK(hipMemsetAsync(d_slab_cost_.ptr, 0, 8, st));
       }
       ReduceArgs R = reduce_args();
       R.lambda = lambda;
@@ -404,8 +393,8 @@ class BAEngine {
       Q.F = F;
       Q.fx = prob_.fx; Q.fy = prob_.fy; Q.cx = prob_.cx; Q.cy = prob_.cy;
       Q.lambda = lambda;
-      Q.huber = huber_;
-      Q.huber2 = huber_ * huber_;
+      Q.huber = sess_.huber;
+      Q.huber2 = sess_.huber * sess_.huber;
       Q.point_ptr = d_cov_ptr_.as<int>();
       Q.pt_inv = d_cov_inv_.as<int>();
       Q.obs_cam = d_obs_cam_.as<int>();
@@ -413,7 +402,7 @@ class BAEngine {
       Q.poses = d_pose_[cur_].as<double>();
       Q.points = d_points_.as<double>();
       Q.cov = d_cov_.as<double>();
-      Q.sqrt_w = weighted_ ? d_sqw_obs_.as<double>() : nullptr;
+      Q.sqrt_w = sess_.weighted ? d_sqw_obs_.as<double>() : nullptr;
       Q.out = d_cov_pts_.as<double>();
       launch_cov_points(Q, st);
       VO_HIP_CHECK(hipGetLastError());
@@ -441,53 +430,35 @@ class BAEngine {
   // problem landmark -> internal landmark map.
   void upload_cov_tables() {
     upload_obs();
-    if (cov_uploaded_) return;
+    if (sess_.cov_uploaded) return;
     const BAPlan& P = plan_;
     hipStream_t st = ctx_->stream;
-    const size_t M = (size_t)P.n_obs;
     // (host sources that live as long as the session: the copies need no synchronisation, and the
     // vectors are rewritten only behind the next setup's)
-    std::vector<int32_t>&ptr = h_cov_ptr_, &inv = h_cov_inv_;
-    ptr.assign(P.n_points + 1, 0);
-    inv.assign(std::max(1, P.n_points), 0);
-    for (int q = 0; q < P.n_points; ++q) inv[P.pt_perm[q]] = q;
-    for (size_t pos = 0; pos < M; ++pos) ++ptr[P.pt_perm[P.te_pt[P.obs_te[pos]]] + 1];
-    for (int p = 0; p < P.n_points; ++p) ptr[p + 1] += ptr[p];
-    upload(d_cov_ptr_, ptr, st);
-    upload(d_cov_inv_, inv, st);
+    csr_tables(P, h_cov_ptr_, h_cov_inv_);
+    upload(d_cov_ptr_, h_cov_ptr_, st);
+    upload(d_cov_inv_, h_cov_inv_, st);
     upload(d_cov_first_, P.prof_first, st);
     upload(d_cov_off_, P.prof_off, st);
     upload(d_cov_last_, P.prof_last, st);
-    upload(d_cov_dst_, red_dst_, st);
+    upload(d_cov_dst_, red_.dst, st);
     d_cov_fail_.reserve(sizeof(int));
-    cov_uploaded_ = true;
+    sess_.cov_uploaded = true;
   }
 
   // The problem-order observation arrays of residuals() and covariance(), sent on a session's
   // first use: rebuilt from the plan's internal-order copies (the caller's arrays are not kept).
   void upload_obs() {
-    if (obs_uploaded_) return;
+    if (sess_.obs_uploaded) return;
     const BAPlan& P = plan_;
     hipStream_t st = ctx_->stream;
-    const size_t M = (size_t)P.n_obs;
-    VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "BA read-out: the plan has no observation order");
+    VO_REQUIRE(P.obs_order.size() >= (size_t)P.n_obs, VO_ERR_STATE, "BA read-out: the plan has no observation order");
     // (session-long host sources, as upload_cov_tables')
-    std::vector<int32_t>&cam = h_obs_cam_, &pt = h_obs_pt_;
-    std::vector<float>& uv = h_obs_uv_;
-    cam.resize(M);
-    pt.resize(M);
-    uv.resize(2 * M);
-    for (size_t pos = 0; pos < M; ++pos) {  // internal position -> problem observation (ba_plan.h)
-      const size_t o = (size_t)P.obs_order[pos];
-      cam[o] = P.obs_cam[pos];
-      pt[o] = P.te_pt[P.obs_te[pos]];
-      uv[2 * o] = P.obs_uv[2 * pos];
-      uv[2 * o + 1] = P.obs_uv[2 * pos + 1];
-    }
-    upload(d_obs_cam_, cam, st);
-    upload(d_obs_pt_, pt, st);
-    upload(d_obs_uv_, uv, st);
-    obs_uploaded_ = true;
+    obs_tables(P, h_obs_cam_, h_obs_pt_, h_obs_uv_);
+    upload(d_obs_cam_, h_obs_cam_, st);
+    upload(d_obs_pt_, h_obs_pt_, st);
+    upload(d_obs_uv_, h_obs_uv_, st);
+    sess_.obs_uploaded = true;
   }
 
   // vo_ba_set_obs_weights: information weights in problem order, null for all ones (the session
@@ -503,7 +474,7 @@ class BAEngine {
                    "vo_ba_set_obs_weights: weight %zu is negative or not finite", o);
     apply_pending();  // under the weights the step was solved with
     if (!w) {
-      weighted_ = false;
+      sess_.weighted = false;
       return;
     }
     upload_weight_tables();
@@ -515,7 +486,7 @@ class BAEngine {
     upload(d_sqw_obs_, so, st);
     upload(d_sqw_plan_, sp, st);
     VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vectors end here
-    weighted_ = true;
+    sess_.weighted = true;
   }
 
   // vo_ba_get_obs_weights: synchronises; what was set, the culled observations at 0.
@@ -524,9 +495,9 @@ class BAEngine {
     VO_REQUIRE(w_out, VO_ERR_ARG, "vo_ba_get_obs_weights: null output");
     const size_t M = (size_t)plan_.n_obs;
     hipStream_t st = ctx_->stream;
-    if (weighted_ && M) VO_HIP_CHECK(hipMemcpyAsync(w_out, d_w_.ptr, M * 8, hipMemcpyDeviceToHost, st));
+    if (sess_.weighted && M) VO_HIP_CHECK(hipMemcpyAsync(w_out, d_w_.ptr, M * 8, hipMemcpyDeviceToHost, st));
     VO_HIP_CHECK(hipStreamSynchronize(st));
-    if (!weighted_) std::fill(w_out, w_out + M, 1.0);
+    if (!sess_.weighted) std::fill(w_out, w_out + M, 1.0);
   }
 
   // vo_ba_cull / _async (vo_hip.h): two kernels on the stream at the device state, nothing but the
@@ -546,13 +517,13 @@ class BAEngine {
     const int M = P.n_obs;
     upload_cov_tables();  // the problem-order observation arrays and CSR
     upload_weight_tables();
-    const bool was_weighted = weighted_;
-    if (!weighted_) {
+    const bool was_weighted = sess_.weighted;
+    if (!sess_.weighted) {
       launch_fill(d_w_.as<double>(), M, 1.0, st);
       launch_fill(d_sqw_obs_.as<double>(), M, 1.0, st);
       launch_fill(d_sqw_plan_.as<double>(), M, 1.0, st);
       VO_HIP_CHECK(hipGetLastError());
-      weighted_ = true;
+      sess_.weighted = true;
     }
     VO_HIP_CHECK(hipMemsetAsync(d_cull_cnt_.ptr, 0, 2 * sizeof(int), st));
     CullArgs C;
@@ -581,24 +552,22 @@ class BAEngine {
     VO_HIP_CHECK(hipStreamSynchronize(st));
     if (n_culled_out) *n_culled_out = cnt[0];
     if (n_active_out) *n_active_out = cnt[1];
-    if (!was_weighted && cnt[0] == 0) weighted_ = false;  // still all ones
+    if (!was_weighted && cnt[0] == 0) sess_.weighted = false;  // still all ones
   }
 
   // The weight arrays and the problem observation -> plan position map, on a session's first use.
   void upload_weight_tables() {
-    if (wt_tables_) return;
+    if (sess_.wt_tables) return;
     const BAPlan& P = plan_;
     const size_t M = (size_t)P.n_obs;
     VO_REQUIRE(P.obs_order.size() >= M, VO_ERR_STATE, "BA weights: the plan has no observation order");
-    std::vector<int32_t>& pos_of = h_obs_pos_;  // (a session-long host source: no synchronisation)
-    pos_of.assign(std::max<size_t>(M, 1), 0);
-    for (size_t pos = 0; pos < M; ++pos) pos_of[(size_t)P.obs_order[pos]] = (int32_t)pos;
-    upload(d_obs_pos_, pos_of, ctx_->stream);
+    obs_positions(P, h_obs_pos_);  // (a session-long host source: no synchronisation)
+    upload(d_obs_pos_, h_obs_pos_, ctx_->stream);
     d_w_.reserve(std::max<size_t>(M, 1) * 8);
     d_sqw_obs_.reserve(std::max<size_t>(M, 1) * 8);
     d_sqw_plan_.reserve(std::max<size_t>(M, 1) * 8);
     d_cull_cnt_.reserve(2 * sizeof(int));
-    wt_tables_ = true;
+    sess_.wt_tables = true;
   }
 
   // iters GN iterations; sync=true finalises and reads the costs back.
@@ -619,11 +588,11 @@ class BAEngine {
     if (!sync) return VO_OK;
     finalize_cost(d_cost_.as<double>() + iters);
     std::vector<double> costs(iters + 1);
-    int status = 0;
+    StatusRead sr;
     VO_HIP_CHECK(hipMemcpyAsync(costs.data(), d_cost_.ptr, costs.size() * 8, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    sr.enqueue(*this);
     VO_HIP_CHECK(hipStreamSynchronize(st));
-    const bool timed_out = clear_failure(status);
+    const auto [status, timed_out] = sr.settle(*this);
     if (status)  // iteration `status` (1-based) failed: the state is its linearisation point
       for (int k = status; k <= iters; ++k) costs[k] = NAN;
     if (cost_out) std::copy(costs.begin(), costs.end(), cost_out);
@@ -648,40 +617,41 @@ class BAEngine {
     VO_REQUIRE(iters >= 0, VO_ERR_ARG, "vo_ba_run_lm: iters < 0");
     VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_run_lm: not with a communicator of more than one rank");
     require_weighted_layout("vo_ba_run_lm");
-    const vo_ba_lm_options o = lm_options(opt);
+    vo_ba_lm_options o;
+    const std::string bad = lm_options(opt, prob_.lambda, o);
+    VO_REQUIRE(bad.empty(), VO_ERR_ARG, "%s", bad.c_str());
     hipStream_t st = ctx_->stream;
     apply_pending();  // a pending GN step: under the lambda and delta it was solved with
-    d_lm_log_.reserve(lm_log_bytes(iters));
+    const LmLog log{iters};
+    d_lm_log_.reserve(log.bytes());
     d_lm_snap_.reserve(24ull * std::max(1, plan_.n_points));
-    lm_iters_ = iters;
-    lm_session_ = session_;
-    lm_unread_ = true;
-    lm_fail_ = 0;
-    lm_timeout_ = false;
     // termination (set_lm_stop): with a criterion set, the decide instantiation that tests it
-    const bool stop = lm_stop_.ftol > 0.0 || lm_stop_.xtol > 0.0 || lm_stop_.max_rejects > 0;
-    lm_stop_on_ = stop;
-    lm_trials_ = iters;
-    lm_reason_ = VO_BA_LM_RAN_ALL;
+    const vo_ba_lm_stop& crit = sess_.lm_stop;
+    const bool stop = crit.ftol > 0.0 || crit.xtol > 0.0 || crit.max_rejects > 0;
+    sess_.lm = LmRun{};  // this run's record: unread, ran all until its first read says otherwise
+    sess_.lm.iters = sess_.lm.trials = iters;
+    sess_.lm.unread = true;
+    sess_.lm.stop_on = stop;
+    char* const base = d_lm_log_.as<char>();
     LmDecideArgs D{};
     D.nseg = std::max(1, plan_.n_segments());
     D.n_points = plan_.n_points;
     D.n_poses = plan_.n_poses;
     D.lambda0 = o.lambda0; D.up = o.up; D.down = o.down; D.lambda_min = o.lambda_min; D.lambda_max = o.lambda_max;
     D.slab_cost = d_slab_cost_.as<double>();
-    D.cost = d_lm_log_.as<double>();
-    D.lambda = D.cost + iters + 1;
-    D.trial = D.lambda + iters + 1;
-    D.accepted = reinterpret_cast<int*>(D.trial + iters);
+    D.cost = reinterpret_cast<double*>(base + log.cost_off());
+    D.lambda = reinterpret_cast<double*>(base + log.lambda_off());
+    D.trial = reinterpret_cast<double*>(base + log.trial_off());
+    D.accepted = reinterpret_cast<int*>(base + log.accepted_off());
     D.points = d_points_.as<double>();
     D.snap = d_lm_snap_.as<double>();
     D.status = d_status_.as<int>();
-    D.ftol = lm_stop_.ftol;
-    D.xtol = lm_stop_.xtol;
-    D.max_rejects = lm_stop_.max_rejects;
+    D.ftol = crit.ftol;
+    D.xtol = crit.xtol;
+    D.max_rejects = crit.max_rejects;
     D.n_dc = 6 * plan_.n_free;
     D.dc = d_dc_.as<double>();
-    D.stop = D.accepted + std::max(1, iters);
+    D.stop = reinterpret_cast<int*>(base + log.stop_off());
     auto decide = [&](int k) {
       D.k = k;
       D.pose_cur = d_pose_[cur_ ^ 1].as<double>();
@@ -722,34 +692,25 @@ class BAEngine {
   // state at the last accepted one; its trial and decision and every later entry are NaN / 0.
   int lm_read(int n, double* cost_out, double* lambda_out, double* trial_out, uint8_t* accepted_out,
               const char* who) {
-    VO_REQUIRE(lm_iters_ >= 0 && lm_session_ == session_, VO_ERR_STATE, "%s: no vo_ba_run_lm on this session", who);
-    VO_REQUIRE(n >= 0 && n <= lm_iters_, VO_ERR_ARG, "%s: n = %d outside the last run's 0..%d iterations", who, n,
-               lm_iters_);
+    const LmRun& lm = sess_.lm;
+    VO_REQUIRE(lm.iters >= 0, VO_ERR_STATE, "%s: no vo_ba_run_lm on this session", who);
+    VO_REQUIRE(n >= 0 && n <= lm.iters, VO_ERR_ARG, "%s: n = %d outside the last run's 0..%d iterations", who, n,
+               lm.iters);
     hipStream_t st = ctx_->stream;
-    const int N = lm_iters_;
-    std::vector<double> log(3 * (size_t)N + 2);
-    std::vector<int> acc(std::max(1, N));
-    VO_HIP_CHECK(hipMemcpyAsync(log.data(), d_lm_log_.ptr, log.size() * 8, hipMemcpyDeviceToHost, st));
-    if (N)
-      VO_HIP_CHECK(hipMemcpyAsync(acc.data(), d_lm_log_.as<double>() + log.size(), N * sizeof(int), hipMemcpyDeviceToHost, st));
+    const LmLog log{lm.iters};
+    std::vector<double> vals(log.accepted_off() / 8);
+    std::vector<int> acc(std::max(1, log.n));
+    VO_HIP_CHECK(hipMemcpyAsync(vals.data(), d_lm_log_.ptr, log.accepted_off(), hipMemcpyDeviceToHost, st));
+    if (log.n)
+      VO_HIP_CHECK(hipMemcpyAsync(acc.data(), d_lm_log_.as<char>() + log.accepted_off(), log.n * sizeof(int),
+                                  hipMemcpyDeviceToHost, st));
     lm_settle();
-    const double *cost = log.data(), *lam = cost + N + 1, *trial = lam + N + 1;
-    // first iteration without a verdict: the failed one, or the first behind a stop, whose cost and
-    // damping (the stopped state's) every later entry repeats
-    const int f = lm_fail_ ? lm_fail_ - 1 : lm_trials_;
-    const bool stopped = !lm_fail_ && lm_reason_ != VO_BA_LM_RAN_ALL;
-    for (int k = 0; k <= n; ++k) {
-      if (cost_out) cost_out[k] = k <= f ? cost[k] : stopped ? cost[f] : NAN;
-      if (lambda_out) lambda_out[k] = k <= f ? lam[k] : stopped ? lam[f] : NAN;
-    }
-    for (int k = 0; k < n; ++k) {
-      if (trial_out) trial_out[k] = k < f ? trial[k] : NAN;
-      if (accepted_out) accepted_out[k] = k < f && acc[k] ? 1 : 0;
-    }
-    VO_REQUIRE(!lm_timeout_, VO_ERR_HIP, "%s: fused reduction timed out at iteration %d (a reducer workgroup never arrived)",
-               who, lm_fail_ - 1);
-    if (lm_fail_) {
-      set_error("%s: reduced camera system not positive definite at iteration %d", who, lm_fail_ - 1);
+    log.decode(vals.data(), acc.data(), n, lm.fail ? lm.fail - 1 : lm.trials, !lm.fail && lm.reason != VO_BA_LM_RAN_ALL,
+               cost_out, lambda_out, trial_out, accepted_out);
+    VO_REQUIRE(!lm.timeout, VO_ERR_HIP, "%s: fused reduction timed out at iteration %d (a reducer workgroup never arrived)",
+               who, lm.fail - 1);
+    if (lm.fail) {
+      set_error("%s: reduced camera system not positive definite at iteration %d", who, lm.fail - 1);
       return VO_ERR_NOT_SPD;
     }
     return VO_OK;
@@ -760,33 +721,36 @@ class BAEngine {
   // behind the log.
   void lm_settle() {
     hipStream_t st = ctx_->stream;
-    int status = 0, words[2] = {0, 0};
-    if (lm_unread_) {
-      VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
-      if (lm_stop_on_)
-        VO_HIP_CHECK(hipMemcpyAsync(words, d_lm_log_.as<char>() + lm_log_bytes(lm_iters_) - sizeof(words),
-                                    sizeof(words), hipMemcpyDeviceToHost, st));
+    LmRun& lm = sess_.lm;
+    StatusRead sr;
+    int words[2] = {0, 0};
+    if (lm.unread) {
+      sr.enqueue(*this);
+      if (lm.stop_on)
+        VO_HIP_CHECK(hipMemcpyAsync(words, d_lm_log_.as<char>() + LmLog{lm.iters}.stop_off(), sizeof(words),
+                                    hipMemcpyDeviceToHost, st));
     }
     VO_HIP_CHECK(hipStreamSynchronize(st));
-    if (!lm_unread_) return;
-    lm_timeout_ = clear_failure(status);
-    lm_fail_ = status;
-    lm_unread_ = false;
-    if (lm_fail_) {
-      lm_trials_ = lm_fail_ - 1;
-      lm_reason_ = VO_BA_LM_FAILED;
+    if (!lm.unread) return;
+    const auto [failed, timed_out] = sr.settle(*this);
+    lm.timeout = timed_out;
+    lm.fail = failed;
+    lm.unread = false;
+    if (lm.fail) {
+      lm.trials = lm.fail - 1;
+      lm.reason = VO_BA_LM_FAILED;
     } else if (words[1] != VO_BA_LM_RAN_ALL) {
-      lm_trials_ = words[0];
-      lm_reason_ = words[1];
+      lm.trials = words[0];
+      lm.reason = words[1];
     }
   }
 
   // vo_ba_lm_stop_info: how the session's last LM run ended.
   void lm_stop_info(int32_t* trials_out, int32_t* reason_out) {
-    VO_REQUIRE(lm_iters_ >= 0 && lm_session_ == session_, VO_ERR_STATE, "vo_ba_lm_stop_info: no vo_ba_run_lm on this session");
+    VO_REQUIRE(sess_.lm.iters >= 0, VO_ERR_STATE, "vo_ba_lm_stop_info: no vo_ba_run_lm on this session");
     lm_settle();
-    if (trials_out) *trials_out = lm_trials_;
-    if (reason_out) *reason_out = lm_reason_;
+    if (trials_out) *trials_out = sess_.lm.trials;
+    if (reason_out) *reason_out = sess_.lm.reason;
   }
 
   // The termination criteria of the later LM runs (vo_hip.h vo_ba_set_lm_stop); null: never stop.
@@ -798,26 +762,38 @@ class BAEngine {
     VO_REQUIRE(v.xtol >= 0.0, VO_ERR_ARG, "vo_ba_set_lm_stop: xtol < 0");
     VO_REQUIRE(v.max_rejects >= 0, VO_ERR_ARG, "vo_ba_set_lm_stop: max_rejects < 0");
     VO_REQUIRE(v.reserved == 0, VO_ERR_ARG, "vo_ba_set_lm_stop: reserved must be 0");
-    lm_stop_ = v;
+    sess_.lm_stop = v;
   }
 
-  // After a failed fused launch (any non-zero status; kBandStatusTimeout: the solver gave up
-  // waiting for its reducers) the reducer counter is re-zeroed -- the stream is synchronised,
-  // so every late reducer has counted itself by now -- and the timeout flag is stripped from
-  // the status word's iteration; a failed iteration's status word is re-zeroed on the device
-  // and the stream synchronised.  Returns whether a timeout was recorded.
-  bool clear_failure(int& status) {
-    hipStream_t st = ctx_->stream;
-    if (status && fuse_ok_) VO_HIP_CHECK(hipMemsetAsync(d_colcnt_.ptr, 0, colcnt_bytes_, st));
-    const bool timed_out = status & kBandStatusTimeout;
-    // (an LM stop word is only ever seen here with a later launch's timeout flag on it: ba_lm_finish)
-    status &= ~(kBandStatusTimeout | kLmStatusStopped);
-    if (status) {
-      VO_HIP_CHECK(hipMemsetAsync(d_status_.ptr, 0, sizeof(int), st));
-      VO_HIP_CHECK(hipStreamSynchronize(st));
+  // One read-back of the status word (run, gn_step, lm_settle): enqueue() the copy, synchronise
+  // (the caller's, with its other copies), then settle().  After a failed fused launch (any
+  // non-zero status; kBandStatusTimeout: the solver gave up waiting for its reducers) the
+  // reducer counter is re-zeroed -- the stream is synchronised, so every late reducer has counted
+  // itself by now -- and the timeout flag is stripped from the status word's iteration; a failed
+  // iteration's status word is re-zeroed on the device and the stream synchronised.
+  struct StatusRead {
+    int word = 0;
+    struct Result {
+      int failed;      // the iteration that failed (1-based), 0: none
+      bool timed_out;  // a timeout was recorded
+    };
+    void enqueue(BAEngine& e) {
+      VO_HIP_CHECK(hipMemcpyAsync(&word, e.d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, e.ctx_->stream));
     }
-    return timed_out;
-  }
+    Result settle(BAEngine& e) const {
+      hipStream_t st = e.ctx_->stream;
+      int status = word;
+      if (status && e.fuse_ok_) VO_HIP_CHECK(hipMemsetAsync(e.d_colcnt_.ptr, 0, e.colcnt_bytes_, st));
+      const bool timed_out = status & kBandStatusTimeout;
+      // (an LM stop word is only ever seen here with a later launch's timeout flag on it: ba_lm_finish)
+      status &= ~(kBandStatusTimeout | kLmStatusStopped);
+      if (status) {
+        VO_HIP_CHECK(hipMemsetAsync(e.d_status_.ptr, 0, sizeof(int), st));
+        VO_HIP_CHECK(hipStreamSynchronize(st));
+      }
+      return {status, timed_out};
+    }
+  };
 
   int gn_step(double* S_out, double* b_out, double* dc_out, double* cost_out) {
     require_state();
@@ -828,40 +804,23 @@ class BAEngine {
     d_cost_.reserve(8);
     enqueue_lin(pending_ ? (kBacksub | kAccum) : kAccum);
     enqueue_reduce();
-    std::vector<double> sys(sys_len_);
+    std::vector<double> sys(red_.sys_len);
     // the reduced system as K2 wrote it: before the solve (the profile solver factors it in
     // place), or after the fused K2 + K3 launch (the banded K3 only reads it)
-    if (!fused()) VO_HIP_CHECK(hipMemcpyAsync(sys.data(), d_sys_.ptr, sys_len_ * 8, hipMemcpyDeviceToHost, st));
+    if (!fused()) VO_HIP_CHECK(hipMemcpyAsync(sys.data(), d_sys_.ptr, sys.size() * 8, hipMemcpyDeviceToHost, st));
     enqueue_solve(1);
-    if (fused()) VO_HIP_CHECK(hipMemcpyAsync(sys.data(), d_sys_.ptr, sys_len_ * 8, hipMemcpyDeviceToHost, st));
+    if (fused()) VO_HIP_CHECK(hipMemcpyAsync(sys.data(), d_sys_.ptr, sys.size() * 8, hipMemcpyDeviceToHost, st));
     std::vector<double> dc(6ull * F);
-    int status = 0;
+    StatusRead sr;
     if (F) VO_HIP_CHECK(hipMemcpyAsync(dc.data(), d_dc_.ptr, dc.size() * 8, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipMemcpyAsync(&status, d_status_.ptr, sizeof(int), hipMemcpyDeviceToHost, st));
+    sr.enqueue(*this);
     VO_HIP_CHECK(hipStreamSynchronize(st));
     cur_ ^= 1;
     pending_ = true;
-    if (S_out) {  // K2's output layout (red_dst_) back to the dense symmetric S
-      const int n = 6 * F;
-      std::fill(S_out, S_out + (size_t)n * n, 0.0);
-      for (int i = 0; i < F; ++i)
-        for (int j = P.prof_first[i]; j <= i; ++j) {
-          const int d = red_dst_[P.prof_off[i] + j - P.prof_first[i]];
-          const double* blk = sys.data() + (d & ~kRedTranspose);
-          const bool tr = d & kRedTranspose;
-          for (int r = 0; r < 6; ++r)
-            for (int c = 0; c < 6; ++c) {
-              const double v = blk[tr ? 6 * c + r : 6 * r + c];
-              S_out[(size_t)(6 * i + r) * n + 6 * j + c] = v;
-              S_out[(size_t)(6 * j + c) * n + 6 * i + r] = v;
-            }
-        }
-    }
-    if (b_out)
-      for (int f = 0; f < F; ++f) std::copy(sys.begin() + red_rdst_[f], sys.begin() + red_rdst_[f] + 6, b_out + 6 * f);
+    dense_system(P, red_, sys.data(), S_out, b_out);  // K2's output layout back to the dense symmetric S, and b
     if (dc_out) std::copy(dc.begin(), dc.end(), dc_out);
-    if (cost_out) *cost_out = sys[cost_off_];
-    const bool timed_out = clear_failure(status);
+    if (cost_out) *cost_out = sys[red_.cost_off];
+    const auto [status, timed_out] = sr.settle(*this);
     if (status) {
       VO_REQUIRE(!timed_out, VO_ERR_HIP, "vo_ba_gn_step: fused reduction timed out (a reducer workgroup never arrived)");
       set_error("vo_ba_gn_step: reduced camera system not positive definite");
@@ -902,30 +861,6 @@ class BAEngine {
   void require_state() const {
     VO_REQUIRE(have_problem_, VO_ERR_STATE, "BA: no problem set up");
     VO_REQUIRE(have_state_, VO_ERR_STATE, "BA: no state set");
-  }
-
-  // The log of an LM run of n iterations: cost (n + 1), lambda (n + 1), trial (n) doubles, then
-  // the n decisions (ints) and the two control words of a stop (trials, reason; LmDecideArgs::stop).
-  static size_t lm_log_bytes(int n) { return (3 * (size_t)n + 2) * 8 + (std::max(1, n) + 2) * sizeof(int); }
-
-  // vo_ba_run_lm's options with the defaults filled in (vo_hip.h); VO_ERR_ARG for a bad field.
-  vo_ba_lm_options lm_options(const vo_ba_lm_options* opt) const {
-    vo_ba_lm_options o = opt ? *opt : vo_ba_lm_options{};
-    VO_REQUIRE(std::isfinite(o.lambda0) && std::isfinite(o.up) && std::isfinite(o.down) &&
-                   std::isfinite(o.lambda_min) && std::isfinite(o.lambda_max),
-               VO_ERR_ARG, "vo_ba_run_lm: non-finite option");
-    if (o.up == 0.0) o.up = 10.0;
-    if (o.down == 0.0) o.down = 0.1;
-    if (o.lambda_min == 0.0) o.lambda_min = 1e-6;
-    if (o.lambda_max == 0.0) o.lambda_max = 1e6;
-    if (o.lambda0 == 0.0) o.lambda0 = prob_.lambda > 0.0 ? prob_.lambda : 1e-4;
-    VO_REQUIRE(o.lambda0 >= 0.0, VO_ERR_ARG, "vo_ba_run_lm: lambda0 < 0");
-    VO_REQUIRE(o.up > 1.0, VO_ERR_ARG, "vo_ba_run_lm: up must be > 1");
-    VO_REQUIRE(o.down > 0.0 && o.down < 1.0, VO_ERR_ARG, "vo_ba_run_lm: down must be in (0, 1)");
-    VO_REQUIRE(o.lambda_min > 0.0 && o.lambda_min <= o.lambda_max, VO_ERR_ARG,
-               "vo_ba_run_lm: need 0 < lambda_min <= lambda_max");
-    o.lambda0 = std::min(std::max(o.lambda0, o.lambda_min), o.lambda_max);
-    return o;
   }
 
   // ---- setup's steps, in its order ----------------------------------------------------------
@@ -1016,47 +951,32 @@ class BAEngine {
       R.n = 0;
       copied = 0;
     };
-    for (int c0 = 0; c0 < nch;) {
-      const int src = c0 < (int)P.chunk_src.size() ? P.chunk_src[c0] : -1;
-      int c1 = c0 + 1;
-      while (c1 < nch && (src < 0 ? P.chunk_src[c1] < 0 : P.chunk_src[c1] == src + (c1 - c0))) ++c1;
-      if (src >= 0) {  // taken over: a run of the copy kernel
+    image_runs(P, img_runs_);
+    for (const ImageRun& r : img_runs_) {
+      if (r.src >= 0) {  // taken over: a run of the copy kernel
         if (R.n == kImgRuns) flush();
-        R.src[R.n] = src;
-        R.dst[R.n] = c0;
-        copied += c1 - c0;
+        R.src[R.n] = r.src;
+        R.dst[R.n] = r.dst;
+        copied += r.count;
         R.end[R.n++] = copied;
       } else {  // built by this plan: from the page-locked images
-        VO_HIP_CHECK(hipMemcpyAsync(d_chunk_img_.as<ChunkImg>() + c0, P.chunk_img.data() + c0,
-                                    (size_t)(c1 - c0) * sizeof(ChunkImg), hipMemcpyHostToDevice, ctx_->stream));
+        VO_HIP_CHECK(hipMemcpyAsync(d_chunk_img_.as<ChunkImg>() + r.dst, P.chunk_img.data() + r.dst,
+                                    (size_t)r.count * sizeof(ChunkImg), hipMemcpyHostToDevice, ctx_->stream));
       }
-      c0 = c1;
     }
     flush();
     plan_ok_ = true;
   }
 
-  // K2's output layout -- the profile [S | b | cost], or the banded K3's columns (and that
-  // solver's layout and tables) --, its per-block table and the fused launch's readiness table.
+  // K2's output layout (ba_tables.h reduce_layout) with the banded K3's own layout and tables,
+  // the system buffer, and whether K2 rides in K3's launch.
   void reduce_tables(TablePack& pack) {
     const BAPlan& P = plan_;
     hipStream_t st = ctx_->stream;
-    const int F = P.n_free, nprof = P.n_prof_blocks();
-    red_dst_.assign(std::max(1, nprof), 0);
-    red_rdst_.assign(std::max(1, F), 0);
+    const int F = P.n_free, w = band_.w;
+    reduce_layout(P, band_on_, w, band_.m + band_.s, band_col_stride(w), red_);
     size_t pad = 0;
     if (band_on_) {
-      const int w = band_.w, CS = band_col_stride(w), top = band_.m + band_.s;
-      const int base_b = top * CS;
-      for (int i = 0; i < F; ++i) {
-        for (int j = P.prof_first[i]; j <= i; ++j) {
-          const int b = P.prof_off[i] + j - P.prof_first[i];
-          red_dst_[b] = i < top ? j * CS + 36 * (i - j) : (base_b + (F - 1 - i) * CS + 36 * (i - j)) | kRedTranspose;
-        }
-        red_rdst_[i] = i < top ? i * CS + 36 * (w + 1) : base_b + (F - 1 - i) * CS + 36 * (w + 1);
-      }
-      sys_len_ = (size_t)(F + band_.s) * CS + 1;
-      cost_off_ = (long)sys_len_ - 1;
       pad = band_slot_stride(w);  // the ring loader's last LDS-DMA piece reads past the end
       band_lds_ = band_lds_layout(F, band_, P.n_poses, !ctx_->ba_no_split);
       band_tab_ = band_tables(F, band_, band_lds_);
@@ -1068,51 +988,21 @@ class BAEngine {
         VO_REQUIRE((size_t)x.end() <= band_fac_doubles(F, w), VO_ERR_STATE, "band split: exchange area");
         VO_HIP_CHECK(hipMemsetAsync(d_fac_.as<double>() + x.flag, 0, 3 * 16 * sizeof(double), st));
       }
-    } else {
-      for (int b = 0; b < nprof; ++b) red_dst_[b] = 36 * b;
-      for (int f = 0; f < F; ++f) red_rdst_[f] = 36 * nprof + 6 * f;
-      sys_len_ = 36ull * nprof + 6ull * F + 1;
-      cost_off_ = (long)sys_len_ - 1;
     }
-    d_sys_.reserve((sys_len_ + pad) * 8);
+    d_sys_.reserve((red_.sys_len + pad) * 8);
     // entries K2 never writes (outside the profile, the bottom side's separator) stay 0
-    VO_HIP_CHECK(hipMemsetAsync(d_sys_.ptr, 0, (sys_len_ + pad) * 8, st));
-    // K2's per-block table: slab rows, the diagonal blocks' rhs entries, output offsets
-    red_meta_.assign(std::max(1, nprof), int4{0, 0, -1, -1});
-    red_out_.assign(std::max(1, nprof), int2{0, 0});
-    for (int i = 0; i < F; ++i)
-      for (int b = P.prof_off[i]; b < P.prof_off[i + 1]; ++b) {
-        const bool diag = P.prof_diag[b] != 0;
-        red_meta_[b] = int4{P.prof_src_ptr[b], P.prof_src_ptr[b + 1], diag ? P.camb_ptr[i] : -1,
-                            diag ? P.camb_ptr[i + 1] : -1};
-        red_out_[b] = int2{red_dst_[b], diag ? red_rdst_[i] : 0};
-      }
-    // the fused launch's readiness counters: the column each profile block's reducer stores
-    // into (top columns j of rows i < m + s, then bottom column F - 1 - i at m + s + F - 1 - i),
-    // the cost at F, and how many items each counter waits for
-    red_col_.assign(std::max(1, nprof), 0);
-    col_need_.assign(F + 1, 0);
-    if (band_on_) {
-      const int top = band_.m + band_.s;
-      for (int i = 0; i < F; ++i)
-        for (int b = P.prof_off[i]; b < P.prof_off[i + 1]; ++b) {
-          const int j = P.prof_first[i] + (b - P.prof_off[i]);
-          red_col_[b] = i < top ? j : top + (F - 1 - i);
-          ++col_need_[red_col_[b]];
-        }
-      col_need_[F] = 1;  // the cost item
-    }
-    pack.add(red_meta_, d_red_meta_);
-    pack.add(red_out_, d_red_out_);
-    pack.add(red_col_, d_red_col_);
-    pack.add(col_need_, d_col_need_);
+    VO_HIP_CHECK(hipMemsetAsync(d_sys_.ptr, 0, (red_.sys_len + pad) * 8, st));
+    pack.add(red_.meta, d_red_meta_);
+    pack.add(red_.out, d_red_out_);
+    pack.add(red_.col, d_red_col_);
+    pack.add(red_.col_need, d_col_need_);
     // K2 fused into the banded K3's launch when every workgroup of it fits one round at
     // one per CU (the solver's LDS): cfg3's 356 blocks make 178 reducers + the solver on
     // MI355X's 256 CUs (fewer CUs, e.g. a partitioned device: K2 stays a launch of its own)
     // (full mode only: the ring-mode solver reads sys with plain loads, so it must come from an
     // earlier launch)
     fuse_ok_ = VO_BA_FUSE && band_on_ && band_lds_.full && !band_lds_.split &&
-               band_fused_workgroups(nprof) + 1 <= ctx_->num_cus;
+               band_fused_workgroups(P.n_prof_blocks()) + 1 <= ctx_->num_cus;
   }
 
   // One page-locked staging buffer, one device buffer, one copy (each table a pageable
@@ -1190,8 +1080,8 @@ class BAEngine {
     A.dc = d_dc_.as<double>();
     A.status = d_status_.as<int>();
     A.stamps = nullptr;
-    A.huber = huber_;
-    A.huber2 = huber_ * huber_;
+    A.huber = sess_.huber;
+    A.huber2 = sess_.huber * sess_.huber;
     A.lm_lambda = lm_lambda_;
     return A;
   }
@@ -1204,30 +1094,43 @@ class BAEngine {
     pending_ = false;
   }
 
-  // mode: kBacksub | kAccum; the Huber instantiations are chosen here (huber_ > 0).
-  void enqueue_lin(int mode) {
+  // What a K1 launch needs: its arguments (nseg set) and the chunks per segment of the one-wave
+  // K1 (0: the four-wave K1).  False without segments (no landmarks: empty slabs, and the zero
+  // cost is written here).
+  struct K1Launch {
+    LinArgs A;
+    int wave_chunks;
+  };
+  bool prepare_k1(K1Launch& k) {
     const int nseg = plan_.n_segments();
     if (nseg <= 0) {
-      // no landmarks: empty slabs, zero cost
       VO_HIP_CHECK(hipMemsetAsync(d_slab_cost_.ptr, 0, 8, ctx_->stream));
-      return;
+      return false;
     }
-    LinArgs A = lin_args();
+    k.A = lin_args();
     // one-wave K1 for plans of one chunk per segment (the chunk image of segment s is chunk s)
     const bool wave = plan_is_wave(plan_.seg_obs);
     const int nw = wave ? plan_.seg_chunks : 1;
     VO_REQUIRE(!wave || ((int64_t)nseg * nw == plan_.n_chunks() && nw >= 1 && nw <= kWaveMaxChunks), VO_ERR_STATE,
                "K1: segments of seg_chunks chunks expected");
-    A.nseg = nseg;
+    k.A.nseg = nseg;
+    k.wave_chunks = wave ? nw : 0;
+    return true;
+  }
+
+  // mode: kBacksub | kAccum; the Huber instantiations are chosen in launch_k1 (a delta > 0).
+  void enqueue_lin(int mode) {
+    K1Launch k;
+    if (!prepare_k1(k)) return;
     ++launches_;
     ctx_->prof.begin(ctx_->stream, kKBaLin);
     if (stamps_on_) {  // one row per chunk (one-wave K1) or segment (four-wave K1)
       d_stamps_.reserve((size_t)plan_.n_chunks() * kPhCount * 8);
-      A.stamps = d_stamps_.as<unsigned long long>();
+      k.A.stamps = d_stamps_.as<unsigned long long>();
     }
     // inside an LM run (lm_lambda_ set) the modes that use the damping read it from the device
     if (lm_lambda_ && mode != 0) mode |= kLm;
-    launch_k1(A, mode, wave ? nw : 0, "BA");
+    launch_k1(k.A, mode, k.wave_chunks, "BA");
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
   }
@@ -1235,7 +1138,7 @@ class BAEngine {
   // A session with observation weights on a K1 layout without a weighted form: refused before
   // anything is enqueued or any run state is touched.
   void require_weighted_layout(const char* who) const {
-    if (!weighted_ || plan_.n_segments() <= 0) return;
+    if (!sess_.weighted || plan_.n_segments() <= 0) return;
     const int nw = plan_is_wave(plan_.seg_obs) ? plan_.seg_chunks : 0;
     VO_REQUIRE(lin_weighted_covers(nw), VO_ERR_STATE,
                "%s: the session has observation weights, and its K1 layout (%s) has no weighted instantiation", who,
@@ -1247,11 +1150,11 @@ class BAEngine {
   // which exist for the one-wave K1 only -- any other layout refuses the run, it never drops the
   // weights.
   void launch_k1(LinArgs& A, int mode, int wave_chunks, const char* who) {
-    if (!weighted_) {
-      launch_lin(A, huber_ > 0.0 ? mode | kRobust : mode, wave_chunks, A.nseg, ctx_->stream);
+    if (!sess_.weighted) {
+      launch_lin(A, sess_.huber > 0.0 ? mode | kRobust : mode, wave_chunks, A.nseg, ctx_->stream);
       return;
     }
-    if (!(huber_ > 0.0)) {
+    if (!(sess_.huber > 0.0)) {
       A.huber = kWeightedNoHuber;
       A.huber2 = kWeightedNoHuber * kWeightedNoHuber;
     }
@@ -1280,7 +1183,7 @@ class BAEngine {
     R.slab_b = d_slab_b_.as<double>();
     R.slab_cost = d_slab_cost_.as<double>();
     R.sys = d_sys_.as<double>();
-    R.cost_off = cost_off_;
+    R.cost_off = red_.cost_off;
     R.status = d_status_.as<int>();
     R.lm_lambda = lm_lambda_;
     return R;
@@ -1294,70 +1197,77 @@ class BAEngine {
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
     if (sharded())
-      ctx_->comm->allreduce(d_sys_.as<double>(), sys_len_, false, ctx_->stream);
+      ctx_->comm->allreduce(d_sys_.as<double>(), red_.sys_len, false, ctx_->stream);
   }
 
-  void launch_solve(const SolveArgs& A, bool chain_next = false) {
-    ++launches_;
-    if (band_on_) {
-      BandArgs B;
-      B.F = A.F;
-      B.w = band_.w;
-      B.m = band_.m;
-      B.nb = band_.nb;
-      B.s = band_.s;
-      B.nprof = A.nprof;
-      B.n_poses = A.n_poses;
-      B.n_fixed = A.n_fixed;
-      B.iter_tag = A.iter_tag;
-      B.cost_off = cost_off_;
-      B.merge = band_tab_.merge;
-      B.n_merge = band_tab_.n_merge;
-      B.tab = d_band_tab_.as<int>();
-      B.sys = A.sys;
-      B.zero = d_zero_.as<double>();
-      B.fac = band_lds_.full && !band_lds_.split ? nullptr : d_fac_.as<double>();
-      // split hand-off flags and the chained launch's publish word (seq << 1 | verdict): new every
-      // launch, the low 31 bits never zero
-      while ((++band_seq_ & 0x7fffffffu) == 0) {
-      }
-      B.seq = band_seq_;
-      B.cost_out = A.cost_out;
-      B.dc = A.dc;
-      B.pose_cur = A.pose_cur;
-      B.pose_next = A.pose_next;
-      B.status = A.status;
-      B.stamps = nullptr;
-      B.nred = fused() ? band_fused_workgroups(A.nprof) : 0;
-      B.red_drop = B.nred > 0 ? ctx_->ba_drop_reducers : 0;
-      B.red_count = d_colcnt_.as<unsigned>();
-      B.red_col = d_red_col_.as<int>();
-      B.col_need = d_col_need_.as<int>();
-      B.red = reduce_args();
-      if (stamps_on_) {  // per wave phase cycles, then realtime stamps of the solver and each reducer
-        d_stamps3_.reserve((8 * kBandStamps + 8 + 4 * (B.nred + 1)) * 8);
-        B.stamps = d_stamps3_.as<unsigned long long>();
-      }
-      if (chain_next) {
-        // the next iteration's K1 (iteration() flips cur_ behind this launch): its pending step's
-        // linearisation point is this solve's input, its own the poses this solve writes
-        B.lin = lin_args();
-        std::swap(B.lin.pose_old, B.lin.pose_new);
-        B.lin.nseg = B.k1_nseg = plan_.n_segments();
-        B.pub_mask = (ctx_->ba_chain_poll ? ctx_->ba_chain_poll : kChainPollReplicas) - 1;
-        B.pub = d_pub_.as<unsigned>();
-        if (stamps_on_) {  // [published, launch start | start, prefix done, gate passed, end per K1 workgroup]
-          d_stamps_k1_.reserve((2 + 4 * (size_t)B.k1_nseg) * 8);
-          B.k1_stamps = d_stamps_k1_.as<unsigned long long>();
-        }
-      }
-      launch_band_solve(B, band_lds_, ctx_->stream);
-      return;
-    }
-    launch_profile_solve(A, solve_lds_, solve_lds_size_, ctx_->stream);
-  }
-
+  // K3 of one iteration (iter_tag: its 1-based number in the status word) on the context stream;
+  // cost_slot, if set, receives the cost of its linearisation; chain_next: iteration().
   void enqueue_solve(int iter_tag, double* cost_slot = nullptr, bool chain_next = false) {
+    ctx_->prof.begin(ctx_->stream, kKBaSolve);
+    ++launches_;
+    if (band_on_) enqueue_band_solve(iter_tag, cost_slot, chain_next);
+    else enqueue_profile_solve(iter_tag, cost_slot);
+    ctx_->prof.end(ctx_->stream);
+    VO_HIP_CHECK(hipGetLastError());
+  }
+
+  void enqueue_band_solve(int iter_tag, double* cost_slot, bool chain_next) {
+    const BAPlan& P = plan_;
+    BandArgs B;
+    B.F = P.n_free;
+    B.w = band_.w;
+    B.m = band_.m;
+    B.nb = band_.nb;
+    B.s = band_.s;
+    B.nprof = P.n_prof_blocks();
+    B.n_poses = P.n_poses;
+    B.n_fixed = P.n_fixed;
+    B.iter_tag = iter_tag;
+    B.cost_off = red_.cost_off;
+    B.merge = band_tab_.merge;
+    B.n_merge = band_tab_.n_merge;
+    B.tab = d_band_tab_.as<int>();
+    B.sys = d_sys_.as<double>();
+    B.zero = d_zero_.as<double>();
+    B.fac = band_lds_.full && !band_lds_.split ? nullptr : d_fac_.as<double>();
+    // split hand-off flags and the chained launch's publish word (seq << 1 | verdict): new every
+    // launch, the low 31 bits never zero
+    while ((++band_seq_ & 0x7fffffffu) == 0) {
+    }
+    B.seq = band_seq_;
+    B.cost_out = cost_slot;
+    B.dc = d_dc_.as<double>();
+    B.pose_cur = d_pose_[cur_].as<double>();
+    B.pose_next = d_pose_[cur_ ^ 1].as<double>();
+    B.status = d_status_.as<int>();
+    B.stamps = nullptr;
+    B.nred = fused() ? band_fused_workgroups(B.nprof) : 0;
+    B.red_drop = B.nred > 0 ? ctx_->ba_drop_reducers : 0;
+    B.red_count = d_colcnt_.as<unsigned>();
+    B.red_col = d_red_col_.as<int>();
+    B.col_need = d_col_need_.as<int>();
+    B.red = reduce_args();
+    if (stamps_on_) {  // per wave phase cycles, then realtime stamps of the solver and each reducer
+      d_stamps3_.reserve((8 * kBandStamps + 8 + 4 * (B.nred + 1)) * 8);
+      B.stamps = d_stamps3_.as<unsigned long long>();
+    }
+    if (chain_next) {
+      // the next iteration's K1 (iteration() flips cur_ behind this launch): its pending step's
+      // linearisation point is this solve's input, its own the poses this solve writes
+      B.lin = lin_args();
+      std::swap(B.lin.pose_old, B.lin.pose_new);
+      B.lin.nseg = B.k1_nseg = plan_.n_segments();
+      B.pub_mask = (ctx_->ba_chain_poll ? ctx_->ba_chain_poll : kChainPollReplicas) - 1;
+      B.pub = d_pub_.as<unsigned>();
+      if (stamps_on_) {  // [published, launch start | start, prefix done, gate passed, end per K1 workgroup]
+        d_stamps_k1_.reserve((2 + 4 * (size_t)B.k1_nseg) * 8);
+        B.k1_stamps = d_stamps_k1_.as<unsigned long long>();
+      }
+    }
+    launch_band_solve(B, band_lds_, ctx_->stream);
+  }
+
+  void enqueue_profile_solve(int iter_tag, double* cost_slot) {
     const BAPlan& P = plan_;
     SolveArgs A;
     A.F = P.n_free;
@@ -1365,9 +1275,8 @@ class BAEngine {
     A.n_poses = P.n_poses;
     A.n_fixed = P.n_fixed;
     A.iter_tag = iter_tag;
-    A.max_panel = std::max(1, P.solve_layout.max_panel);
-    A.max_row_span = 0;
-    for (int k = 0; k < P.n_free; ++k) A.max_row_span = std::max(A.max_row_span, k - P.prof_first[k]);
+    A.max_panel = solve_max_panel_;
+    A.max_row_span = solve_max_row_span_;
     A.lds_kf = (long)solve_layout_.kf;
     A.lds_y = (long)solve_layout_.y;
     A.lds_panel = (long)solve_layout_.panel;
@@ -1386,10 +1295,7 @@ class BAEngine {
       d_stamps3_.reserve(kS3Count * 8);
       A.stamps = d_stamps3_.as<unsigned long long>();
     }
-    ctx_->prof.begin(ctx_->stream, kKBaSolve);
-    launch_solve(A, chain_next);
-    ctx_->prof.end(ctx_->stream);
-    VO_HIP_CHECK(hipGetLastError());
+    launch_profile_solve(A, solve_lds_, solve_lds_size_, ctx_->stream);
   }
 
   // lin_done: this iteration's K1 rode in the previous solve launch; chain_next: this solve
@@ -1412,7 +1318,7 @@ class BAEngine {
     return VO_BA_CHAIN && !ctx_->ba_no_chain && band_on_ && fused() && band_lds_.full && !band_lds_.split &&
            plan_is_wave(plan_.seg_obs) && plan_.seg_chunks == kBandChainChunks && nseg > 0 &&
            (int64_t)nseg * kBandChainChunks == plan_.n_chunks() && nseg + 2 <= ctx_->num_cus && !lm_lambda_ &&
-           !weighted_ &&  // observation weights: the separate K1 launch (the chained K1 has no weighted form)
+           !sess_.weighted &&  // observation weights: the separate K1 launch (the chained K1 has no weighted form)
            !ctx_->prof.on && (!stamps_on_ || ctx_->ba_chain_stamps) && !sharded();
   }
 
@@ -1458,7 +1364,8 @@ class BAEngine {
   bool have_problem_ = false, have_state_ = false, pending_ = false, solve_lds_ = false;
   uint64_t session_ = 0;
   int cur_ = 0;
-  size_t sys_len_ = 0, solve_lds_size_ = 0;
+  size_t solve_lds_size_ = 0;
+  int solve_max_panel_ = 1, solve_max_row_span_ = 0;  // the profile K3's SolveArgs constants (setup)
   SolveLds solve_layout_{};
   BandSplit band_{};
   bool band_on_ = false;
@@ -1482,12 +1389,9 @@ class BAEngine {
   int last_launches_ = 0, launches_ = 0;
   size_t colcnt_bytes_ = 0;
   DevView d_red_col_, d_col_need_;
-  std::vector<int32_t> red_col_, col_need_;
-  std::vector<int4> red_meta_;
-  std::vector<int2> red_out_;
+  ReduceLayout red_;  // K2's output layout and tables (host copies: gn_step, covariance)
+  std::vector<ImageRun> img_runs_;  // upload_images' runs
   DevBuf d_fac_;
-  std::vector<int32_t> red_dst_, red_rdst_;  // K2 output offsets (host copies for gn_step)
-  long cost_off_ = 0;
   HostBuf h_state_;  // page-locked staging of set_state / get_state
   hipEvent_t h_state_ev_ = nullptr;  // set_state's upload from h_state_ done
   bool h_state_busy_ = false;
@@ -1530,32 +1434,40 @@ class BAEngine {
  private:
   DevBuf d_points_, d_pose_[2], d_dc_, d_slab_, d_slab_b_, d_slab_cost_, d_sys_;
   DevBuf d_cost_, d_cost_tmp_;
-  double huber_ = 0.0;  // Huber delta in pixels, 0: plain cost (set_robust)
+  // What belongs to the current problem and to nothing else: setup() starts every session from
+  // Session{}, so nothing here outlives its problem.
+  struct LmRun {  // the last vo_ba_run_lm, as lm_read needs it
+    int iters = -1;  // -1: no LM run on this session yet
+    int fail = 0;    // the failed iteration (1-based), 0: none
+    bool timeout = false, unread = false;
+    // termination: whether the run tested a criterion, and how it ended (settled at its first read)
+    bool stop_on = false;
+    int trials = 0, reason = VO_BA_LM_RAN_ALL;
+  };
+  struct Session {
+    double huber = 0.0;  // Huber delta in pixels, 0: plain cost (set_robust)
+    // observation weights (set_obs_weights, cull): whether the session has any (false: every
+    // launch is the unweighted one, every observation at weight 1)
+    bool weighted = false;
+    // the lazy tables, each sent on the session's first call that needs it: upload_obs,
+    // upload_cov_tables, upload_weight_tables
+    bool obs_uploaded = false, cov_uploaded = false, wt_tables = false;
+    vo_ba_lm_stop lm_stop{};  // the LM runs' termination criteria (all zero: never stop)
+    LmRun lm;
+  };
+  Session sess_;
   // step control (run_lm): the damping's device address while an LM run enqueues its kernels
-  // (null otherwise: the GN kernels), the log and the landmark snapshot, and what lm_read needs
+  // (null otherwise: the GN kernels), the log and the landmark snapshot
   const double* lm_lambda_ = nullptr;
   DevBuf d_lm_log_, d_lm_snap_;
-  int lm_iters_ = -1, lm_fail_ = 0;
-  uint64_t lm_session_ = 0;
-  bool lm_unread_ = false, lm_timeout_ = false;
-  // termination: the session's criteria (all zero: never stop), whether the last run tested any,
-  // and how it ended (settled at its first read)
-  vo_ba_lm_stop lm_stop_{};
-  bool lm_stop_on_ = false;
-  int lm_trials_ = 0, lm_reason_ = VO_BA_LM_RAN_ALL;
-  // residuals(): the problem-order observation arrays (uploaded on a session's first call) and
-  // its output [err2 | depth]
-  bool obs_uploaded_ = false;
+  // residuals(): the problem-order observation arrays and its output [err2 | depth]
   DevBuf d_obs_cam_, d_obs_pt_, d_obs_uv_, d_obs_out_;
-  // covariance(): its tables (uploaded on a session's first call), the dense factor and inverse
-  // of S, the landmark blocks and the factorisation's failure word
-  bool cov_uploaded_ = false;
+  // covariance(): its tables, the dense factor and inverse of S, the landmark blocks and the
+  // factorisation's failure word
   DevBuf d_cov_ptr_, d_cov_inv_, d_cov_first_, d_cov_off_, d_cov_last_, d_cov_dst_;
   DevBuf d_cov_l_, d_cov_, d_cov_pts_, d_cov_fail_;
-  // observation weights (set_obs_weights, cull): whether the session has any (false: every launch
-  // is the unweighted one), w and sqrt(w) in problem order, sqrt(w) in the plan's order (K1), the
+  // observation weights: w and sqrt(w) in problem order, sqrt(w) in the plan's order (K1), the
   // problem observation -> plan position map and the cull's two counters
-  bool weighted_ = false, wt_tables_ = false;
   DevBuf d_w_, d_sqw_obs_, d_sqw_plan_, d_obs_pos_, d_cull_cnt_;
   // host sources of the read-outs' and the cull's tables (upload_obs, upload_cov_tables,
   // upload_weight_tables): kept for the session, so their copies need no synchronisation

@@ -1,0 +1,169 @@
+// The BA engine's host arithmetic (ba_tables.h).
+#include "ba_tables.h"
+
+#include <cmath>
+
+namespace vo {
+
+void reduce_layout(const BAPlan& P, bool band_on, int w, int top, int col_stride, ReduceLayout& L) {
+  const int F = P.n_free, nprof = P.n_prof_blocks();
+  L.dst.assign(std::max(1, nprof), 0);
+  L.rdst.assign(std::max(1, F), 0);
+  if (band_on) {
+    const int CS = col_stride;
+    const int s = top < F ? w : 0;  // the separator: w rows of a two-sided split, none one-sided (top = F)
+    const int base_b = top * CS;
+    for (int i = 0; i < F; ++i) {
+      for (int j = P.prof_first[i]; j <= i; ++j) {
+        const int b = P.prof_off[i] + j - P.prof_first[i];
+        L.dst[b] = i < top ? j * CS + 36 * (i - j) : (base_b + (F - 1 - i) * CS + 36 * (i - j)) | kTabTranspose;
+      }
+      L.rdst[i] = i < top ? i * CS + 36 * (w + 1) : base_b + (F - 1 - i) * CS + 36 * (w + 1);
+    }
+    L.sys_len = (size_t)(F + s) * CS + 1;
+    L.cost_off = (long)L.sys_len - 1;
+  } else {
+    for (int b = 0; b < nprof; ++b) L.dst[b] = 36 * b;
+    for (int f = 0; f < F; ++f) L.rdst[f] = 36 * nprof + 6 * f;
+    L.sys_len = 36ull * nprof + 6ull * F + 1;
+    L.cost_off = (long)L.sys_len - 1;
+  }
+  // K2's per-block table: slab rows, the diagonal blocks' rhs entries, output offsets
+  L.meta.assign(4 * (size_t)std::max(1, nprof), 0);
+  L.meta[2] = L.meta[3] = -1;
+  L.out.assign(2 * (size_t)std::max(1, nprof), 0);
+  for (int i = 0; i < F; ++i)
+    for (int b = P.prof_off[i]; b < P.prof_off[i + 1]; ++b) {
+      const bool diag = P.prof_diag[b] != 0;
+      int32_t* m = &L.meta[4 * (size_t)b];
+      m[0] = P.prof_src_ptr[b];
+      m[1] = P.prof_src_ptr[b + 1];
+      m[2] = diag ? P.camb_ptr[i] : -1;
+      m[3] = diag ? P.camb_ptr[i + 1] : -1;
+      L.out[2 * (size_t)b] = L.dst[b];
+      L.out[2 * (size_t)b + 1] = diag ? L.rdst[i] : 0;
+    }
+  L.col.assign(std::max(1, nprof), 0);
+  L.col_need.assign(F + 1, 0);
+  if (band_on) {
+    for (int i = 0; i < F; ++i)
+      for (int b = P.prof_off[i]; b < P.prof_off[i + 1]; ++b) {
+        const int j = P.prof_first[i] + (b - P.prof_off[i]);
+        L.col[b] = i < top ? j : top + (F - 1 - i);
+        ++L.col_need[L.col[b]];
+      }
+    L.col_need[F] = 1;  // the cost item
+  }
+}
+
+void dense_system(const BAPlan& P, const ReduceLayout& L, const double* sys, double* S_out, double* b_out) {
+  const int F = P.n_free;
+  if (S_out) {
+    const int n = 6 * F;
+    std::fill(S_out, S_out + (size_t)n * n, 0.0);
+    for (int i = 0; i < F; ++i)
+      for (int j = P.prof_first[i]; j <= i; ++j) {
+        const int d = L.dst[P.prof_off[i] + j - P.prof_first[i]];
+        const double* blk = sys + (d & ~kTabTranspose);
+        const bool tr = d & kTabTranspose;
+        for (int r = 0; r < 6; ++r)
+          for (int c = 0; c < 6; ++c) {
+            const double v = blk[tr ? 6 * c + r : 6 * r + c];
+            S_out[(size_t)(6 * i + r) * n + 6 * j + c] = v;
+            S_out[(size_t)(6 * j + c) * n + 6 * i + r] = v;
+          }
+      }
+  }
+  if (b_out)
+    for (int f = 0; f < F; ++f) std::copy(sys + L.rdst[f], sys + L.rdst[f] + 6, b_out + 6 * f);
+}
+
+void obs_tables(const BAPlan& P, std::vector<int32_t>& cam, std::vector<int32_t>& pt, std::vector<float>& uv) {
+  const size_t M = (size_t)P.n_obs;
+  cam.resize(M);
+  pt.resize(M);
+  uv.resize(2 * M);
+  for (size_t pos = 0; pos < M; ++pos) {  // internal position -> problem observation (ba_plan.h)
+    const size_t o = (size_t)P.obs_order[pos];
+    cam[o] = P.obs_cam[pos];
+    pt[o] = P.te_pt[P.obs_te[pos]];
+    uv[2 * o] = P.obs_uv[2 * pos];
+    uv[2 * o + 1] = P.obs_uv[2 * pos + 1];
+  }
+}
+
+void csr_tables(const BAPlan& P, std::vector<int32_t>& ptr, std::vector<int32_t>& inv) {
+  const size_t M = (size_t)P.n_obs;
+  ptr.assign(P.n_points + 1, 0);
+  inv.assign(std::max(1, P.n_points), 0);
+  for (int q = 0; q < P.n_points; ++q) inv[P.pt_perm[q]] = q;
+  for (size_t pos = 0; pos < M; ++pos) ++ptr[P.pt_perm[P.te_pt[P.obs_te[pos]]] + 1];
+  for (int p = 0; p < P.n_points; ++p) ptr[p + 1] += ptr[p];
+}
+
+void obs_positions(const BAPlan& P, std::vector<int32_t>& pos_of) {
+  const size_t M = (size_t)P.n_obs;
+  pos_of.assign(std::max<size_t>(M, 1), 0);
+  for (size_t pos = 0; pos < M; ++pos) pos_of[(size_t)P.obs_order[pos]] = (int32_t)pos;
+}
+
+void image_runs(const BAPlan& P, std::vector<ImageRun>& runs) {
+  const int nch = (int)P.chunk_img.size();
+  runs.clear();
+  for (int c0 = 0; c0 < nch;) {
+    const int src = P.chunk_src[c0];
+    int c1 = c0 + 1;
+    while (c1 < nch && (src < 0 ? P.chunk_src[c1] < 0 : P.chunk_src[c1] == src + (c1 - c0))) ++c1;
+    runs.push_back({src < 0 ? -1 : src, c0, c1 - c0});
+    c0 = c1;
+  }
+}
+
+ReserveWindow reserve_window(int n_poses, int n_points, int64_t n_obs) {
+  const int len0 = (int)std::min<int64_t>(n_poses, n_obs / n_points);
+  const int64_t extra = std::min<int64_t>(n_obs - (int64_t)len0 * n_points, n_points);
+  ReserveWindow W;
+  std::vector<int32_t>&ptr = W.point_ptr, &cam = W.obs_cam;
+  ptr.assign(n_points + 1, 0);
+  cam.reserve(n_obs);
+  for (int p = 0; p < n_points; ++p) {
+    const int len = std::min(n_poses, len0 + (p < extra ? 1 : 0));
+    const int c0 = (int)((int64_t)p * (n_poses - len + 1) / n_points);
+    for (int c = 0; c < len; ++c) cam.push_back(c0 + c);
+    ptr[p + 1] = (int32_t)cam.size();
+  }
+  return W;
+}
+
+void LmLog::decode(const double* doubles, const int* acc, int n_asked, int f, bool stopped, double* cost_out,
+                   double* lambda_out, double* trial_out, uint8_t* accepted_out) const {
+  const double *cost = doubles, *lam = cost + n + 1, *trial = lam + n + 1;
+  for (int k = 0; k <= n_asked; ++k) {
+    if (cost_out) cost_out[k] = k <= f ? cost[k] : stopped ? cost[f] : NAN;
+    if (lambda_out) lambda_out[k] = k <= f ? lam[k] : stopped ? lam[f] : NAN;
+  }
+  for (int k = 0; k < n_asked; ++k) {
+    if (trial_out) trial_out[k] = k < f ? trial[k] : NAN;
+    if (accepted_out) accepted_out[k] = k < f && acc[k] ? 1 : 0;
+  }
+}
+
+std::string lm_options(const vo_ba_lm_options* opt, double problem_lambda, vo_ba_lm_options& o) {
+  o = opt ? *opt : vo_ba_lm_options{};
+  if (!(std::isfinite(o.lambda0) && std::isfinite(o.up) && std::isfinite(o.down) && std::isfinite(o.lambda_min) &&
+        std::isfinite(o.lambda_max)))
+    return "vo_ba_run_lm: non-finite option";
+  if (o.up == 0.0) o.up = 10.0;
+  if (o.down == 0.0) o.down = 0.1;
+  if (o.lambda_min == 0.0) o.lambda_min = 1e-6;
+  if (o.lambda_max == 0.0) o.lambda_max = 1e6;
+  if (o.lambda0 == 0.0) o.lambda0 = problem_lambda > 0.0 ? problem_lambda : 1e-4;
+  if (!(o.lambda0 >= 0.0)) return "vo_ba_run_lm: lambda0 < 0";
+  if (!(o.up > 1.0)) return "vo_ba_run_lm: up must be > 1";
+  if (!(o.down > 0.0 && o.down < 1.0)) return "vo_ba_run_lm: down must be in (0, 1)";
+  if (!(o.lambda_min > 0.0 && o.lambda_min <= o.lambda_max)) return "vo_ba_run_lm: need 0 < lambda_min <= lambda_max";
+  o.lambda0 = std::min(std::max(o.lambda0, o.lambda_min), o.lambda_max);
+  return "";
+}
+
+}  // namespace vo
