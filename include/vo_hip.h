@@ -378,6 +378,66 @@ typedef struct {
 int vo_ba_cull(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt, int32_t* n_culled_out,
                int32_t* n_active_out);
 int vo_ba_cull_async(vo_ctx* ctx, uint64_t session, const vo_ba_cull_options* opt);
+/* Pose prior.  vo_ba_setup_prior is vo_ba_setup with a quadratic cost on the leading free poses,
+ * e.g. the Schur complement of what left a sliding window.  prior == NULL is vo_ba_setup itself:
+ * the same plan, digests, launches and bits.
+ * For free pose f < K let xi_f = (rho, phi) be the twist that the solver's own update map
+ * T <- exp(delta^) T takes poses0[f] to the current pose by: the SE(3) log of T_f T0_f^-1 (the
+ * exp map's coefficients, series below its threshold included, so the two are inverses; pose
+ * differences of less than pi).  With xi the 6K stacked entries, every cost the API reports
+ * (vo_ba_run, vo_ba_run_lm costs and trials, vo_ba_gn_step) gains
+ *   E_prior = cost0 - 2 eta^T xi + xi^T Lambda xi,
+ * and the reduced system S dc = b of every linearisation becomes
+ *   (S + Lambda^) dc = b + (eta^ - Lambda^ xi^),     ^: padded with zeros to 6F,
+ * which uses the first-order Jacobian d xi / d delta ~ I of the log (exact at xi = 0, the state a
+ * marginalisation hands over; the right Jacobian of the log is not applied).  The prior is not
+ * robustified, weighted or culled; the problem's lambda and LM's are added as without it.
+ * vo_ba_gn_step's S_out and b_out and vo_ba_covariance include it (it is part of S);
+ * vo_ba_residuals and vo_ba_cull do not see it.  Every sum runs in a fixed order: two runs from one
+ * state agree bit for bit, and a rejected LM step still restores poses and points bit for bit.
+ * The prior couples its poses pairwise, so the profile of S has a dense leading K x K block
+ * triangle; the banded solver stays in use while the widened bandwidth fits it (K <= 10 keeps a
+ * window of tracks of at most 10 cameras banded), the profile solver takes over otherwise.  A session
+ * with a prior runs K1 and the prior's kernel as launches of their own, never inside the solve
+ * launch; without one every launch is the one vo_ba_setup's session makes.
+ * VO_ERR_ARG: K < 1, K > n_poses - n_fixed (or beyond 440: the prior's kernel keeps xi,
+ * Lambda xi and its partial sums in 64 KiB of LDS), reserved != 0, a null array or any non-finite value.
+ * VO_ERR_STATE: a communicator of more than one rank (a prior over landmark shards is not built).
+ * A system that is not positive definite fails as without a prior. */
+typedef struct {
+  int32_t n_poses;       /* K >= 1: the prior covers free poses 0..K-1 (window cameras n_fixed..n_fixed+K-1) */
+  int32_t reserved;      /* 0 */
+  const double* info;    /* (6K,6K) row-major Lambda; the lower triangle is read and mirrored */
+  const double* rhs;     /* (6K) eta */
+  const double* poses0;  /* (K,12) linearisation poses, laid out as vo_ba_set_state */
+  double cost0;
+} vo_ba_pose_prior;
+int vo_ba_setup_prior(vo_ctx* ctx, const vo_ba_problem* prob, const vo_ba_pose_prior* prior, uint64_t* session_out);
+/* Marginalisation: the prior that a slide by n_drop cameras leaves, computed at the device-resident
+ * state (after any pending landmark update).  Nothing else is written: poses, points, weights, the
+ * LM log and the status word are afterwards what they were, as after vo_ba_covariance.
+ * D = window cameras 0..n_drop-1 (1 <= n_drop < n_poses); P_D = the landmarks with at least one
+ * active observation in D (point_marg_out[p] = 1, problem order, n_points bytes).  Marginalised are
+ * all active observations of P_D's landmarks, with the session's weights and Huber scale as the
+ * linearisation applies them, and the session's prior, if it has one, in full: the new prior
+ * replaces the old one.  Eliminated are P_D's landmarks (the 3x3 route of every step; a frozen
+ * landmark leaves the system but stays marked) and the m = max(0, n_drop - n_fixed) leading free
+ * poses (a dense Cholesky Schur complement); lambda >= 0 is added to the eliminated blocks only.
+ * With R = (n_poses - n_fixed) - m remaining free poses, outputs (any may be NULL):
+ *   info_out (6R, 6R) row-major, symmetric bit for bit; rhs_out (6R);
+ *   *n_prior_out = K: 1 + the last remaining pose the prior touches (0: none); rows and columns
+ *     beyond 6K are exact zeros;
+ *   poses0_out (R, 12): the current poses of the remaining free cameras;
+ *   *cost0_out: the marginalised factors' cost at this state, so xi = 0 there.
+ * The caller's next window drops D and P_D, sets n_fixed' = max(0, n_fixed - n_drop) and passes the
+ * leading K x K blocks of info_out, with rhs_out, poses0_out and cost0_out, as its prior.
+ * VO_ERR_NOT_SPD: an eliminated pose block fails its pivot test; the outputs are NaN (the mask is
+ * still written) and the session stays usable.  VO_ERR_ARG: n_drop outside 1..n_poses-1, lambda
+ * negative or not finite, or the panel of 6R x 6m doubles with the eliminated block does not fit
+ * 160 KiB of LDS.  VO_ERR_STATE: a stale session, no state set, a communicator of more than one
+ * rank, or a K1 layout without a weighted form (the observation mask acts as weights). */
+int vo_ba_marginalize(vo_ctx* ctx, uint64_t session, int n_drop, double lambda, int32_t* n_prior_out, double* info_out,
+                      double* rhs_out, double* poses0_out, double* cost0_out, uint8_t* point_marg_out);
 /* One-call convenience: setup + set_state + run + get_state. */
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points,
                 int iters, double* cost_out);

@@ -58,6 +58,12 @@ class BACullOptionsC(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class BAPosePriorC(C.Structure):
+    """``vo_ba_pose_prior``: a quadratic cost on the leading K free poses of a window."""
+    _fields_ = [("n_poses", C.c_int32), ("reserved", C.c_int32), ("info", C.POINTER(C.c_double)),
+                ("rhs", C.POINTER(C.c_double)), ("poses0", C.POINTER(C.c_double)), ("cost0", C.c_double)]
+
+
 # vo_ba_lm_stop_info's reasons (VO_BA_LM_*)
 BA_LM_FAILED, BA_LM_RAN_ALL, BA_LM_FTOL, BA_LM_XTOL, BA_LM_REJECTS = -1, 0, 1, 2, 3
 BA_LM_REASONS = {BA_LM_FAILED: "failed", BA_LM_RAN_ALL: "ran_all", BA_LM_FTOL: "ftol", BA_LM_XTOL: "xtol",
@@ -122,6 +128,8 @@ SIGNATURES = {
     "vo_ba_get_obs_weights": (_I, [_P, C.c_uint64, _PD]),
     "vo_ba_cull": (_I, [_P, C.c_uint64, C.POINTER(BACullOptionsC), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vo_ba_cull_async": (_I, [_P, C.c_uint64, C.POINTER(BACullOptionsC)]),
+    "vo_ba_setup_prior": (_I, [_P, C.POINTER(BAProblemC), C.POINTER(BAPosePriorC), C.POINTER(C.c_uint64)]),
+    "vo_ba_marginalize": (_I, [_P, C.c_uint64, _I, _D, _PI32, _PD, _PD, _PD, _PD, C.POINTER(C.c_uint8)]),
     "vo_ba_solve": (_I, [_P, C.POINTER(BAProblemC), _PD, _PD, _I, _PD]),
     "vo_ba_plan_stats": (_I, [_P, _PI64, _I]),
     "vo_ba_debug_stamps": (_I, [_P, C.POINTER(C.c_uint64), _I]),

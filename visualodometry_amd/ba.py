@@ -45,6 +45,14 @@ residual, then the tracks left shorter than ``min_track``.  ``cull_rounds = R`` 
 with ``ba_cull_chi2`` / ``ba_cull_min_depth``) makes ``optimize`` run ``R + 1`` solves with a cull
 between them; ``BAResult.obs_active`` says what survived (``tests/ba_weight_ref.py`` restates both on
 the oracle).
+
+Pose prior (off by default): ``BAWindow.prior`` / ``BASession(..., prior=PosePrior(...))`` add a
+quadratic cost ``cost0 - 2 eta^T xi + xi^T Lambda xi`` on the leading free poses, ``xi`` the se(3)
+log of each pose against its linearisation pose (``vo_ba_setup_prior``) -- the form in which what
+left a sliding window stays in its cost; the solve honours it in every linearisation and every
+reported cost (``tests/ba_prior_ref.py`` restates it on the oracle).  ``BASession.marginalize(n)`` /
+``optimize(..., marginalize=n)`` compute that prior on the device for the window's first ``n``
+cameras (``vo_ba_marginalize``): ``BAResult.prior`` and ``BAResult.point_marginalised``.
 """
 
 from __future__ import annotations
@@ -54,7 +62,23 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BACullOptionsC, BALmOptionsC, BALmStopC, BAProblemC, C, VoError, check, ptr
+from ._lib import BACullOptionsC, BALmOptionsC, BALmStopC, BAPosePriorC, BAProblemC, C, VoError, check, ptr
+
+
+@dataclass
+class PosePrior:
+    """A quadratic cost on the leading ``K`` free poses of a window (``vo_ba_pose_prior``):
+    ``cost0 - 2 rhs^T xi + xi^T info xi``, with ``xi`` (6K) the stacked se(3) logs ``(rho, phi)`` of
+    ``T_f T0_f^-1`` against the linearisation poses ``poses0``."""
+
+    info: np.ndarray  # (6K,6K) Lambda, symmetric (the lower triangle is read)
+    rhs: np.ndarray  # (6K,) eta
+    poses0: np.ndarray  # (K,4,4) linearisation poses, world -> camera
+    cost0: float = 0.0
+
+    @property
+    def n_poses(self) -> int:
+        return int(np.asarray(self.poses0).shape[0])
 
 
 @dataclass
@@ -74,6 +98,8 @@ class BAWindow:
     # (M,) information weights (1 / sigma^2, px^-2) in the window's own observation order, 0 for an
     # observation that does not count; None: all ones
     obs_weight: np.ndarray | None = None
+    # a quadratic cost on the leading free poses (cameras n_fixed .. n_fixed + K - 1); None: none
+    prior: PosePrior | None = None
 
 
 @dataclass
@@ -106,6 +132,11 @@ class BAResult:
     # culling (cull_rounds > 0): which observations were still active after the last solve, in the
     # window's own observation order; cost_per_iter then concatenates the parts' costs
     obs_active: np.ndarray | None = None
+    # optimize(marginalize=n): the prior that dropping the first n cameras leaves at the returned
+    # state (None when it touches no remaining pose, or when the elimination was not positive
+    # definite) and the (L,) bool mask of the landmarks it absorbed, in the window's landmark order
+    prior: PosePrior | None = None
+    point_marginalised: np.ndarray | None = None
 
 
 def poses_to_rt(poses_cw: np.ndarray) -> np.ndarray:
@@ -187,6 +218,22 @@ def _problem_struct(K, point_ptr, obs_cam, obs_uv, n_poses, n_fixed, lam):
     return prob
 
 
+def _prior_struct(prior: PosePrior):
+    """``(vo_ba_pose_prior, the arrays it points into)``; shapes are checked here, before the
+    library reads past a short array."""
+    poses0 = np.asarray(prior.poses0, dtype=np.float64)
+    if poses0.ndim != 3 or poses0.shape[1:] != (4, 4):
+        raise ValueError("PosePrior.poses0 must be (K,4,4)")
+    k = poses0.shape[0]
+    info = np.ascontiguousarray(prior.info, dtype=np.float64)
+    rhs = np.ascontiguousarray(prior.rhs, dtype=np.float64).reshape(-1)
+    if info.shape != (6 * k, 6 * k) or rhs.size != 6 * k:
+        raise ValueError("PosePrior: info must be (6K,6K) and rhs (6K,) for poses0 (K,4,4)")
+    rt = np.ascontiguousarray(poses_to_rt(poses0))
+    pc = BAPosePriorC(k, 0, ptr(info, C.c_double), ptr(rhs, C.c_double), ptr(rt, C.c_double), float(prior.cost0))
+    return pc, (info, rhs, rt)
+
+
 def plan_probe(K, point_ptr, obs_cam, obs_uv, n_poses: int, n_fixed: int = 2,
                target_segments: int = 512) -> dict:
     """Host-only static plan statistics (no device needed): ``vo_ba_plan_probe``."""
@@ -248,7 +295,8 @@ class BASession:
     """
 
     def __init__(self, K, point_ptr, obs_cam, obs_uv, n_poses: int, n_fixed: int = 2,
-                 lam: float = 0.0, ctx: _lib.Context | None = None, huber: float = 0.0):
+                 lam: float = 0.0, ctx: _lib.Context | None = None, huber: float = 0.0,
+                 prior: PosePrior | None = None):
         self.ctx = ctx or _lib.context()
         self.point_ptr = np.ascontiguousarray(point_ptr, dtype=np.int32)
         self.obs_cam = np.ascontiguousarray(obs_cam, dtype=np.int32)
@@ -260,7 +308,14 @@ class BASession:
                                self.n_fixed, lam)
         self._prob = prob
         sid = C.c_uint64(0)
-        check(self.ctx.lib.vo_ba_setup(self.ctx.handle, C.byref(prob), C.byref(sid)), "vo_ba_setup")
+        self.prior = prior
+        if prior is None:
+            check(self.ctx.lib.vo_ba_setup(self.ctx.handle, C.byref(prob), C.byref(sid)), "vo_ba_setup")
+        else:
+            pc, keep = _prior_struct(prior)
+            check(self.ctx.lib.vo_ba_setup_prior(self.ctx.handle, C.byref(prob), C.byref(pc), C.byref(sid)),
+                  "vo_ba_setup_prior")
+            del keep  # (the library copied the arrays)
         # the problem's id on this context: a later setup on the same context (another
         # session) makes every call below fail with VO_ERR_STATE instead of misreading
         self.session = int(sid.value)
@@ -331,6 +386,28 @@ class BASession:
                                            ptr(full, C.c_double) if dense else None, ptr(pts, C.c_double))
         check(rc, "vo_ba_covariance")
         return (pose, pts, full) if dense else (pose, pts)
+
+    def marginalize(self, n_drop: int, lam: float = 0.0):
+        """``(PosePrior | None, point_mask)``: the prior that dropping the window's first ``n_drop``
+        cameras leaves at the device state (``vo_ba_marginalize``) -- over the next window's leading
+        free poses, ``None`` when it touches none -- and the (L,) bool mask of the landmarks it
+        absorbed, which the next window leaves out.  ``lam`` damps the eliminated blocks only.
+        Raises ``VoError`` with ``code == VO_ERR_NOT_SPD`` when an eliminated pose block is not
+        positive definite (the session stays usable)."""
+        r = (self.n_poses - self.n_fixed) - max(0, int(n_drop) - self.n_fixed)
+        info = np.empty((6 * max(r, 0), 6 * max(r, 0)))
+        rhs = np.empty(6 * max(r, 0))
+        poses0 = np.empty((max(r, 0), 12))
+        cost0, k = C.c_double(0.0), C.c_int32(0)
+        mask = np.zeros(max(self.n_points, 1), dtype=np.uint8)
+        check(self.ctx.lib.vo_ba_marginalize(self.ctx.handle, self.session, int(n_drop), float(lam), C.byref(k),
+                                             ptr(info, C.c_double), ptr(rhs, C.c_double), ptr(poses0, C.c_double),
+                                             C.byref(cost0), ptr(mask, C.c_uint8)), "vo_ba_marginalize")
+        k = int(k.value)
+        mask = mask[:self.n_points].astype(bool)
+        if k == 0:
+            return None, mask
+        return PosePrior(info[:6 * k, :6 * k].copy(), rhs[:6 * k].copy(), rt_to_poses(poses0[:k]), float(cost0.value)), mask
 
     def set_state(self, poses_cw: np.ndarray, points: np.ndarray) -> None:
         rt = np.ascontiguousarray(poses_to_rt(poses_cw))
@@ -498,7 +575,8 @@ class SlidingWindowBA:
         n_obs = max(2 * n_points, int(round(obs_per_point * n_points)))
         _lib.ba_reserve(_lib.context(self.device), max(2, int(n_poses)), n_points, n_obs, int(n_fixed))
 
-    def optimize(self, window: BAWindow, return_residuals: bool = False, return_covariance: bool = False) -> BAResult:
+    def optimize(self, window: BAWindow, return_residuals: bool = False, return_covariance: bool = False,
+                 marginalize: int = 0) -> BAResult:
         poses = np.asarray(window.poses_cw, dtype=np.float64)
         pts = np.asarray(window.points, dtype=np.float64).reshape(-1, 3)
         n_fixed = min(int(window.n_fixed), poses.shape[0])
@@ -507,10 +585,10 @@ class SlidingWindowBA:
             return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", "empty window")
         point_ptr, obs_cam, obs_uv, order = group_window(pts.shape[0], window, return_order=True)
         ctx = _lib.context(self.device)
-        err2 = depth = pose_cov = point_cov = sigma2 = None
+        err2 = depth = pose_cov = point_cov = sigma2 = new_prior = marg_mask = None
         try:
             sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
-                             huber=self.huber)
+                             huber=self.huber, prior=window.prior)
             sess.set_state(poses, pts)
             if window.obs_weight is not None:
                 w = np.asarray(window.obs_weight, dtype=np.float64).reshape(-1)
@@ -565,6 +643,17 @@ class SlidingWindowBA:
                     if e.code != _lib.VO_ERR_NOT_SPD:
                         raise
                     pose_cov = point_cov = sigma2 = None
+            if marginalize > 0 and rc == _lib.VO_OK:
+                # what the next window keeps of its first `marginalize` cameras (landmarks keep the
+                # window's own indices).  The solve stands whatever becomes of this: an elimination
+                # that is not positive definite, a panel beyond the kernel's LDS (VO_ERR_ARG) or a K1
+                # layout without a weighted form (VO_ERR_STATE) all mean "no prior"
+                try:
+                    new_prior, marg_mask = sess.marginalize(marginalize, self.lam)
+                except VoError as e:
+                    if e.code not in (_lib.VO_ERR_NOT_SPD, _lib.VO_ERR_ARG, _lib.VO_ERR_STATE):
+                        raise
+                    new_prior = marg_mask = None
         except VoError as e:
             if e.code == _lib.VO_ERR_ARG:
                 return BAResult(poses.copy(), pts.copy(), np.zeros(0), "skipped", str(e))
@@ -572,4 +661,4 @@ class SlidingWindowBA:
         status = "ok" if rc == _lib.VO_OK else "not_spd"
         return BAResult(P, X, costs, status, obs_err2=err2, obs_depth=depth, lambdas=lambdas, accepted=accepted,
                         lm_trials=lm_trials, lm_stop=lm_stop, pose_cov=pose_cov, point_cov=point_cov, cov_sigma2=sigma2,
-                        obs_active=active)
+                        obs_active=active, prior=new_prior, point_marginalised=marg_mask)

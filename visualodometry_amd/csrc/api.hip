@@ -10,6 +10,7 @@
 #include "ba_comm.h"
 #include "ba_engine.h"
 #include "ba_plan.h"
+#include "ba_tables.h"
 #include "vo_ctx.h"
 #include "../../include/vo_hip_testing.h"
 #include "../../include/vo_hip_testing_chain.h"
@@ -715,6 +716,19 @@ int vo_ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_f
   });
 }
 
+int vo_ba_setup_prior(vo_ctx* ctx, const vo_ba_problem* prob, const vo_ba_pose_prior* prior, uint64_t* session_out) {
+  if (!prior) return vo_ba_setup(ctx, prob, session_out);
+  return guarded([&] {
+    // the prior's own fields first: they need no device (nor a context)
+    const std::string bad = vo::pose_prior_error(prob, prior);
+    VO_REQUIRE(bad.empty(), VO_ERR_ARG, "%s", bad.c_str());
+    vo::bind(ctx);
+    VO_REQUIRE(session_out, VO_ERR_ARG, "vo_ba_setup_prior: null session_out");
+    *session_out = 0;
+    *session_out = vo::ba_setup(ctx, prob, prior);
+  });
+}
+
 int vo_ba_set_state(vo_ctx* ctx, uint64_t session, const double* poses, const double* points) {
   return ba_call(ctx, session, [&] { vo::ba_set_state(ctx, poses, points); },
                  poses && points ? nullptr : "vo_ba_set_state: null arrays");
@@ -773,6 +787,13 @@ int vo_ba_covariance(vo_ctx* ctx, uint64_t session, double lambda, double* pose_
                      double* point_cov_out) {
   return ba_call(ctx, session,
                  [&] { return vo::ba_covariance(ctx, lambda, pose_cov_out, pose_dense_out, point_cov_out); });
+}
+
+int vo_ba_marginalize(vo_ctx* ctx, uint64_t session, int n_drop, double lambda, int32_t* n_prior_out, double* info_out,
+                      double* rhs_out, double* poses0_out, double* cost0_out, uint8_t* point_marg_out) {
+  return ba_call(ctx, session, [&] {
+    return vo::ba_marginalize(ctx, n_drop, lambda, n_prior_out, info_out, rhs_out, poses0_out, cost0_out, point_marg_out);
+  });
 }
 
 int vo_ba_set_obs_weights(vo_ctx* ctx, uint64_t session, const double* w) {

@@ -10,7 +10,7 @@ struct vo_ctx;
 
 namespace vo {
 
-uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p);
+uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p, const vo_ba_pose_prior* prior = nullptr);
 void ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_fixed);
 void ba_check_session(vo_ctx* ctx, uint64_t session);
 void ba_set_state(vo_ctx* ctx, const double* poses, const double* pts);
@@ -25,6 +25,8 @@ void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason);
 void ba_set_robust(vo_ctx* ctx, double huber_delta);
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth);
 int ba_covariance(vo_ctx* ctx, double lambda, double* pose_cov, double* pose_dense, double* point_cov);
+int ba_marginalize(vo_ctx* ctx, int n_drop, double lambda, int32_t* n_prior, double* info, double* rhs, double* poses0,
+                   double* cost0, uint8_t* mask);
 void ba_set_obs_weights(vo_ctx* ctx, const double* w);
 void ba_get_obs_weights(vo_ctx* ctx, double* w_out);
 void ba_cull(vo_ctx* ctx, const vo_ba_cull_options* opt, int32_t* n_culled, int32_t* n_active, bool sync);

@@ -16,6 +16,7 @@
 #include "ba_cov.h"
 #include "ba_kernels.h"
 #include "ba_plan.h"
+#include "ba_prior.h"
 #include "ba_tables.h"
 #include "ba_weights.h"
 #include "vo_ctx.h"
@@ -107,7 +108,9 @@ class BAEngine {
   // Returns the new session id.  Every argument and plan check completes before any
   // collective: with a communicator, all ranks then agree (min all-reduce of [ok, F, -F])
   // and fail together, so one rank's bad shard is an error everywhere, not a hang.
-  uint64_t setup(const vo_ba_problem* prob) {
+  // prior: a pose prior over the leading free poses (vo_ba_setup_prior; its fields checked by the
+  // caller, ba_tables.h pose_prior_error), null for none.
+  uint64_t setup(const vo_ba_problem* prob, const vo_ba_pose_prior* prior = nullptr) {
     PLAN_T_START();
     for (int64_t& v : setup_clock().ns) v = 0;
     // the previous setup's chunk-image DMA may still read the page-locked images the
@@ -121,6 +124,8 @@ class BAEngine {
     // unchanged first-camera groups (ba_plan.h build_plan)
     const bool prev_ok = plan_ok_;
     plan_ok_ = false;
+    VO_REQUIRE(!prior || !sharded(), VO_ERR_STATE,
+               "vo_ba_setup_prior: not with a communicator of more than one rank");
     if (err.empty()) err = plan_window(*prob, prev_ok);  // sections 1 - 4
     agree_on_plan(err);
     VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_setup: %s", err.c_str());
@@ -129,12 +134,17 @@ class BAEngine {
     PLAN_T(6, "setup: images");
     std::vector<int32_t> first = local_profile_first(plan_);
     allreduce_min(first);
+    // a pose prior couples its poses pairwise: a dense leading triangle of the profile
+    const int prior_k = prior ? prior->n_poses : 0;
+    VO_REQUIRE(prior_k <= plan_.n_free && prior_lds_bytes(prior_k) <= kPriorLdsMax, VO_ERR_ARG,
+               "vo_ba_setup_prior: a prior over %d poses (free poses: %d)", prior_k, plan_.n_free);
+    for (int i = 0; i < prior_k; ++i) first[i] = 0;
     // banded K3 when the block bandwidth and F fit it (decided on first[], before the
     // profile, whose step tables only the profile solver reads); the profile solver otherwise
     const int F = plan_.n_free;
     band_ = band_split(F, std::vector<int>(first.begin(), first.end()));
     band_on_ = F > 0 && band_supported(F, band_.w, plan_.n_poses);
-    build_profile(plan_, first, !band_on_);
+    build_profile(plan_, first, !band_on_, prior_k);
     PLAN_T(7, "setup: profile");
     prob_ = *prob;
     prob_.point_ptr = nullptr;
@@ -154,9 +164,10 @@ class BAEngine {
     d_pose_[0].reserve(P.n_poses * 96ull);
     d_pose_[1].reserve(P.n_poses * 96ull);
     d_dc_.reserve(std::max(1, F) * 48ull);
-    d_slab_.reserve(std::max(1, P.n_slab_slots()) * 288ull);
-    d_slab_b_.reserve(std::max<size_t>(1, P.segcam_f.size()) * 48ull);
-    d_slab_cost_.reserve(std::max(1, P.n_segments()) * 8ull);
+    // (with a prior: its slab rows, rhs entries and cost entry behind K1's, build_profile)
+    d_slab_.reserve(std::max(1, prior_k ? P.prof_src_ptr.back() : P.n_slab_slots()) * 288ull);
+    d_slab_b_.reserve(std::max<size_t>(1, prior_k ? P.camb_ptr.back() : P.segcam_f.size()) * 48ull);
+    d_slab_cost_.reserve((std::max(1, P.n_segments()) + (prior_k ? 1 : 0)) * 8ull);
     if (!band_on_) {
       pack.add(P.solve_tab, d_solve_tab_);
       const SolveTableLayout& TL = P.solve_layout;
@@ -186,9 +197,62 @@ class BAEngine {
     pending_ = false;
     cur_ = 0;
     sess_ = Session{};  // nothing of the previous problem's settings, lazy tables or LM run
+    prior_k_ = 0;
+    if (prior_k) upload_prior(*prior);
     session_ = ++g_ba_sessions;
     return session_;
   }
+
+  // The prior's arrays -- Lambda with its lower triangle mirrored, eta, the linearisation poses --
+  // and the slab rows build_profile gave it, in one buffer: [Lambda | eta | poses0 | rows (ints)].
+  void upload_prior(const vo_ba_pose_prior& pr) {
+    const BAPlan& P = plan_;
+    hipStream_t st = ctx_->stream;
+    const int K = pr.n_poses;
+    const size_t n = 6ull * K, nblk = (size_t)K * (K + 1) / 2;
+    std::vector<double> h(n * n + n + 12ull * K + (nblk + K + 1) / 2 + 1);
+    for (size_t r = 0; r < n; ++r)
+      for (size_t c = 0; c <= r; ++c) h[r * n + c] = h[c * n + r] = pr.info[r * n + c];
+    std::copy(pr.rhs, pr.rhs + n, h.begin() + n * n);
+    std::copy(pr.poses0, pr.poses0 + 12ull * K, h.begin() + n * n + n);
+    int32_t* rows = reinterpret_cast<int32_t*>(h.data() + n * n + n + 12ull * K);
+    for (int i = 0; i < K; ++i) {
+      for (int j = 0; j <= i; ++j) rows[(size_t)i * (i + 1) / 2 + j] = P.prof_src_ptr[P.prof_off[i] + j + 1] - 1;
+      rows[nblk + i] = P.camb_ptr[i + 1] - 1;
+    }
+    upload(d_prior_, h, st);
+    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vector ends here
+    prior_k_ = K;
+    prior_staged_ = false;
+    prior_cost0_ = pr.cost0;
+  }
+
+  // The prior's kernel behind a K1 launch (or in its place, in a window without segments): the
+  // prior's slab sources and its cost entry at the poses K1 linearised at.
+  void enqueue_prior(const int* status) {
+    if (!prior_k_) return;
+    const size_t n = 6ull * prior_k_, nblk = (size_t)prior_k_ * (prior_k_ + 1) / 2;
+    PriorArgs A;
+    A.K = prior_k_;
+    A.n_fixed = plan_.n_fixed;
+    A.stage = prior_staged_ ? 0 : 1;  // Lambda's slab rows: written once, nothing else touches them
+    prior_staged_ = true;
+    A.cost0 = prior_cost0_;
+    A.info = d_prior_.as<double>();
+    A.rhs = A.info + n * n;
+    A.poses0 = A.rhs + n;
+    A.poses = d_pose_[cur_].as<double>();
+    A.blk_row = reinterpret_cast<const int*>(A.poses0 + 12ull * prior_k_);
+    A.cam_row = A.blk_row + nblk;
+    A.slab = d_slab_.as<double>();
+    A.slab_b = d_slab_b_.as<double>();
+    A.cost = d_slab_cost_.as<double>() + std::max(1, plan_.n_segments());
+    A.status = status;
+    launch_prior(A, ctx_->stream);
+    VO_HIP_CHECK(hipGetLastError());
+  }
+  // The cost entries K2, the LM decision and finalize_cost sum: the segments' and the prior's.
+  int cost_entries() const { return std::max(1, plan_.n_segments()) + (prior_k_ ? 1 : 0); }
 
   // Pre-sizes what a window of about (n_poses, n_points, n_obs) needs, outside the keyframe
   // calls: both plan objects' host arrays (plan_ and prev_plan_ alternate between setups; the
@@ -352,6 +416,7 @@ class BAEngine {
         launch_k1(k1.A, kAccum, k1.wave_chunks, "vo_ba_covariance");
         VO_HIP_CHECK(hipGetLastError());
       }
+      enqueue_prior(nullptr);  // the prior is part of S
       ReduceArgs R = reduce_args();
       R.lambda = lambda;
       R.lm_lambda = nullptr;
@@ -422,6 +487,126 @@ class BAEngine {
         for (int r = 0; r < 6; ++r)
           std::copy(dense + (6ull * f + r) * n + 6ull * f, dense + (6ull * f + r) * n + 6ull * f + 6,
                     pose_cov_out + 36ull * f + 6 * r);
+    return VO_OK;
+  }
+
+  // vo_ba_marginalize (include/vo_hip.h, DESIGN.md §Pose prior): the prior a slide by n_drop cameras
+  // leaves, at the device state.  A kernel marks P_D and builds the masked weights; K1 in accumulate
+  // mode under them (lambda on the landmark blocks), the session's prior and the stand-alone K2
+  // (no camera damping) leave the marginalised factors' system and cost in d_sys_; then the dense
+  // gather and the Schur complement of the eliminated poses (ba_prior.hip).  As in covariance(),
+  // nothing is solved and nothing but the pending update is written to the state.
+  int marginalize(int n_drop, double lambda, int32_t* n_prior_out, double* info_out, double* rhs_out,
+                  double* poses0_out, double* cost0_out, uint8_t* mask_out) {
+    require_state();
+    VO_REQUIRE(!sharded(), VO_ERR_STATE, "vo_ba_marginalize: not with a communicator of more than one rank");
+    const BAPlan& P = plan_;
+    VO_REQUIRE(n_drop >= 1 && n_drop < P.n_poses, VO_ERR_ARG, "vo_ba_marginalize: n_drop must be in 1 .. n_poses - 1");
+    VO_REQUIRE(std::isfinite(lambda) && lambda >= 0.0, VO_ERR_ARG, "vo_ba_marginalize: lambda must be finite and >= 0");
+    const int F = P.n_free, L = P.n_points, m = std::max(0, n_drop - P.n_fixed), R = F - m;
+    VO_REQUIRE(R >= 1, VO_ERR_ARG, "vo_ba_marginalize: no free pose remains");
+    VO_REQUIRE(marg_lds_bytes(F, m) <= kMargLdsMax, VO_ERR_ARG,
+               "vo_ba_marginalize: the panel of %d x %d doubles (with the eliminated block) exceeds 160 KiB of LDS",
+               6 * R, 6 * m);
+    const int nw = plan_is_wave(P.seg_obs) ? P.seg_chunks : 0;
+    VO_REQUIRE(P.n_segments() <= 0 || lin_weighted_covers(nw), VO_ERR_STATE,
+               "vo_ba_marginalize: this K1 layout has no weighted instantiation (the observation mask acts as weights)");
+    hipStream_t st = ctx_->stream;
+    apply_pending();
+    upload_cov_tables();
+    upload_weight_tables();
+    const size_t M = (size_t)P.n_obs, n = 6ull * F, nr = 6ull * R;
+    // scratch: [masked sqrt(w), plan order (M) | b (6F) | rhs (6R) | rdst (ints, F) | fail (int) | mask (L bytes)]
+    const size_t ints_off = (M + n + nr) * 8, mask_off = ints_off + ((size_t)F + 2) * 4;
+    d_marg_.reserve(mask_off + std::max(1, L));
+    double* d_sqw = d_marg_.as<double>();
+    int* d_rdst = reinterpret_cast<int*>(d_marg_.as<char>() + ints_off);
+    int* d_fail = d_rdst + F;
+    unsigned char* d_mask = reinterpret_cast<unsigned char*>(d_marg_.as<char>() + mask_off);
+    VO_HIP_CHECK(hipMemcpyAsync(d_rdst, red_.rdst.data(), (size_t)F * 4, hipMemcpyHostToDevice, st));  // (a session-long source)
+    VO_HIP_CHECK(hipMemsetAsync(d_fail, 0, sizeof(int), st));
+    MargMaskArgs K;
+    K.n_points = L;
+    K.n_drop = n_drop;
+    K.point_ptr = d_cov_ptr_.as<int>();
+    K.obs_cam = d_obs_cam_.as<int>();
+    K.obs_pos = d_obs_pos_.as<int>();
+    K.sqw_obs = sess_.weighted ? d_sqw_obs_.as<double>() : nullptr;
+    K.sqw_plan = d_sqw;
+    K.mask = d_mask;
+    launch_marg_mask(K, st);
+    VO_HIP_CHECK(hipGetLastError());
+    K1Launch k1;
+    if (prepare_k1(k1)) {
+      k1.A.lambda = lambda;
+      k1.A.lm_lambda = nullptr;
+      k1.A.status = nullptr;
+      if (!(sess_.huber > 0.0)) {
+        k1.A.huber = kWeightedNoHuber;
+        k1.A.huber2 = kWeightedNoHuber * kWeightedNoHuber;
+      }
+      const bool ok = launch_lin_weighted(k1.A, d_sqw, kAccum, k1.wave_chunks, k1.A.nseg, st);
+      VO_REQUIRE(ok, VO_ERR_STATE, "vo_ba_marginalize: no weighted K1 instantiation for this layout");
+      VO_HIP_CHECK(hipGetLastError());
+    }
+    enqueue_prior(nullptr);  // the session's prior is marginalised in full
+    ReduceArgs Rd = reduce_args();
+    Rd.lambda = 0.0;  // the damping goes on the eliminated blocks only (ba_marg_kernel)
+    Rd.lm_lambda = nullptr;
+    Rd.status = nullptr;
+    launch_reduce(Rd, Rd.nprof + 1, st);
+    VO_HIP_CHECK(hipGetLastError());
+    d_cov_l_.reserve(n * n * 8);
+    d_cov_.reserve(n * n * 8);
+    VO_HIP_CHECK(hipMemsetAsync(d_cov_l_.ptr, 0, n * n * 8, st));
+    MargArgs A;
+    A.F = F;
+    A.m = m;
+    A.lambda = lambda;
+    A.first = d_cov_first_.as<int>();
+    A.off = d_cov_off_.as<int>();
+    A.dst = d_cov_dst_.as<int>();
+    A.rdst = d_rdst;
+    A.sys = d_sys_.as<double>();
+    A.dense = d_cov_l_.as<double>();
+    A.bvec = d_sqw + M;
+    A.info = d_cov_.as<double>();
+    A.rhs = d_sqw + M + n;
+    A.fail = d_fail;
+    launch_marg_gather(A, st);
+    VO_HIP_CHECK(hipGetLastError());
+    launch_marg(A, st);
+    VO_HIP_CHECK(hipGetLastError());
+    int fail = 0;
+    std::vector<double> info(nr * nr), rhs(nr);
+    std::vector<uint8_t> mask(std::max(1, L));
+    double cost0 = 0.0;
+    VO_HIP_CHECK(hipMemcpyAsync(&fail, d_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(info.data(), A.info, nr * nr * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(rhs.data(), A.rhs, nr * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(&cost0, A.sys + red_.cost_off, 8, hipMemcpyDeviceToHost, st));
+    if (L) VO_HIP_CHECK(hipMemcpyAsync(mask.data(), d_mask, L, hipMemcpyDeviceToHost, st));
+    if (poses0_out)
+      VO_HIP_CHECK(hipMemcpyAsync(poses0_out, d_pose_[cur_].as<double>() + 12ull * (P.n_fixed + m), 96ull * R,
+                                  hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    if (mask_out) std::copy(mask.begin(), mask.begin() + L, mask_out);
+    if (fail) {
+      if (info_out) std::fill(info_out, info_out + nr * nr, (double)NAN);
+      if (rhs_out) std::fill(rhs_out, rhs_out + nr, (double)NAN);
+      if (poses0_out) std::fill(poses0_out, poses0_out + 12ull * R, (double)NAN);
+      if (cost0_out) *cost0_out = NAN;
+      if (n_prior_out) *n_prior_out = 0;
+      set_error("vo_ba_marginalize: the eliminated pose block is not positive definite at row %d", fail - 1);
+      return VO_ERR_NOT_SPD;
+    }
+    int k = 0;  // 1 + the last remaining pose the prior touches
+    for (size_t e = 0; e < nr * nr; ++e)
+      if (info[e] != 0.0) k = std::max(k, (int)(e / nr / 6) + 1);
+    if (n_prior_out) *n_prior_out = k;
+    if (info_out) std::copy(info.begin(), info.end(), info_out);
+    if (rhs_out) std::copy(rhs.begin(), rhs.end(), rhs_out);
+    if (cost0_out) *cost0_out = cost0;
     return VO_OK;
   }
 
@@ -634,7 +819,7 @@ class BAEngine {
     sess_.lm.stop_on = stop;
     char* const base = d_lm_log_.as<char>();
     LmDecideArgs D{};
-    D.nseg = std::max(1, plan_.n_segments());
+    D.nseg = cost_entries();
     D.n_points = plan_.n_points;
     D.n_poses = plan_.n_poses;
     D.lambda0 = o.lambda0; D.up = o.up; D.down = o.down; D.lambda_min = o.lambda_min; D.lambda_max = o.lambda_max;
@@ -1121,7 +1306,7 @@ class BAEngine {
   // mode: kBacksub | kAccum; the Huber instantiations are chosen in launch_k1 (a delta > 0).
   void enqueue_lin(int mode) {
     K1Launch k;
-    if (!prepare_k1(k)) return;
+    if (!prepare_k1(k)) return enqueue_prior(d_status_.as<int>());
     ++launches_;
     ctx_->prof.begin(ctx_->stream, kKBaLin);
     if (stamps_on_) {  // one row per chunk (one-wave K1) or segment (four-wave K1)
@@ -1133,6 +1318,7 @@ class BAEngine {
     launch_k1(k.A, mode, k.wave_chunks, "BA");
     ctx_->prof.end(ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
+    enqueue_prior(k.A.status);
   }
 
   // A session with observation weights on a K1 layout without a weighted form: refused before
@@ -1173,7 +1359,7 @@ class BAEngine {
     ReduceArgs R;
     R.nprof = P.n_prof_blocks();
     R.F = P.n_free;
-    R.nseg = std::max(P.n_segments(), plan_.n_segments() > 0 ? 0 : 1);
+    R.nseg = cost_entries();
     // damping on the camera diagonal: added once -- by rank 0 only when the partial
     // systems of the landmark shards are all-reduced
     R.lambda = (ctx_->comm && ctx_->comm->rank > 0) ? 0.0 : prob_.lambda;
@@ -1319,6 +1505,7 @@ class BAEngine {
            plan_is_wave(plan_.seg_obs) && plan_.seg_chunks == kBandChainChunks && nseg > 0 &&
            (int64_t)nseg * kBandChainChunks == plan_.n_chunks() && nseg + 2 <= ctx_->num_cus && !lm_lambda_ &&
            !sess_.weighted &&  // observation weights: the separate K1 launch (the chained K1 has no weighted form)
+           !prior_k_ &&        // a pose prior: its kernel runs between K1 and the solve launch
            !ctx_->prof.on && (!stamps_on_ || ctx_->ba_chain_stamps) && !sharded();
   }
 
@@ -1331,7 +1518,7 @@ class BAEngine {
     ReduceArgs R{};
     R.nprof = 0;
     R.F = 0;
-    R.nseg = std::max(1, plan_.n_segments());
+    R.nseg = cost_entries();
     R.slab_cost = d_slab_cost_.as<double>();
     R.sys = d_cost_tmp();
     R.cost_off = 0;
@@ -1456,6 +1643,12 @@ class BAEngine {
     LmRun lm;
   };
   Session sess_;
+  // the session's pose prior (setup): its size (0: none), cost0 and device arrays (upload_prior)
+  int prior_k_ = 0;
+  bool prior_staged_ = false;
+  double prior_cost0_ = 0.0;
+  DevBuf d_prior_;
+  DevBuf d_marg_;  // marginalize()'s scratch
   // step control (run_lm): the damping's device address while an LM run enqueues its kernels
   // (null otherwise: the GN kernels), the log and the landmark snapshot
   const double* lm_lambda_ = nullptr;
@@ -1480,7 +1673,9 @@ BAEngine* ba_engine(vo_ctx* ctx) {
   if (!ctx->ba) ctx->ba.reset(new BAEngine(ctx));
   return ctx->ba.get();
 }
-uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p) { return ba_engine(ctx)->setup(p); }
+uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p, const vo_ba_pose_prior* prior) {
+  return ba_engine(ctx)->setup(p, prior);
+}
 void ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_fixed) {
   ba_engine(ctx)->reserve(n_poses, n_points, n_obs, n_fixed);
 }
@@ -1504,6 +1699,10 @@ void ba_set_lm_stop(vo_ctx* ctx, const vo_ba_lm_stop* stop) { ba_engine(ctx)->se
 void ba_lm_stop_info(vo_ctx* ctx, int32_t* trials, int32_t* reason) { ba_engine(ctx)->lm_stop_info(trials, reason); }
 void ba_set_robust(vo_ctx* ctx, double delta) { ba_engine(ctx)->set_robust(delta); }
 void ba_residuals(vo_ctx* ctx, double* err2, double* depth) { ba_engine(ctx)->residuals(err2, depth); }
+int ba_marginalize(vo_ctx* ctx, int n_drop, double lambda, int32_t* n_prior, double* info, double* rhs, double* poses0,
+                   double* cost0, uint8_t* mask) {
+  return ba_engine(ctx)->marginalize(n_drop, lambda, n_prior, info, rhs, poses0, cost0, mask);
+}
 int ba_covariance(vo_ctx* ctx, double lambda, double* pose_cov, double* pose_dense, double* point_cov) {
   return ba_engine(ctx)->covariance(lambda, pose_cov, pose_dense, point_cov);
 }

@@ -1233,7 +1233,7 @@ std::vector<int32_t> local_profile_first(const BAPlan& P) {
   return first;
 }
 
-void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_tables) {
+void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_tables, int prior_k) {
   const int F = P.n_free;
   P.prof_first = first;
   filled(P.prof_off, F + 1, 0);
@@ -1254,8 +1254,14 @@ void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_table
     sblk[s] = P.prof_off[P.slot_i[s]] + (P.slot_j[s] - first[P.slot_i[s]]);
     ++P.prof_src_ptr[sblk[s] + 1];
   }
+  // a pose prior's sources (prior_k > 0): one more slab row behind the slots of every block of
+  // its leading triangle, one more rhs entry behind those of each of its cameras (source -1)
+  size_t nprior = 0;
+  for (int i = 0; i < prior_k; ++i)
+    for (int j = first[i]; j <= i; ++j, ++nprior) ++P.prof_src_ptr[P.prof_off[i] + (j - first[i]) + 1];
   for (int b = 0; b < nb; ++b) P.prof_src_ptr[b + 1] += P.prof_src_ptr[b];
-  sized(P.prof_src, nslot);
+  if (nprior) filled(P.prof_src, nslot + nprior, -1);
+  else sized(P.prof_src, nslot);
   filled(P.slab_pos, std::max<size_t>(nslot, 1), 0);
   {
     std::vector<int32_t> next(P.prof_src_ptr.begin(), P.prof_src_ptr.end() - 1);
@@ -1267,8 +1273,10 @@ void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_table
   }
   filled(P.camb_ptr, F + 1, 0);
   for (size_t e = 0; e < nent; ++e) ++P.camb_ptr[P.segcam_f[e] + 1];
+  for (int f = 0; f < prior_k; ++f) ++P.camb_ptr[f + 1];
   for (int f = 0; f < F; ++f) P.camb_ptr[f + 1] += P.camb_ptr[f];
-  sized(P.camb_src, nent);
+  if (prior_k > 0) filled(P.camb_src, nent + prior_k, -1);
+  else sized(P.camb_src, nent);
   filled(P.cam_pos, std::max<size_t>(nent, 1), 0);
   {
     std::vector<int32_t> next(P.camb_ptr.begin(), P.camb_ptr.end() - 1);

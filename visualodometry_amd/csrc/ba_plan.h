@@ -324,8 +324,12 @@ std::string build_plan(BAPlan& plan, int n_poses, int n_points, int n_obs, int n
 std::vector<int32_t> local_profile_first(const BAPlan& plan);
 // Builds the profile and the K2 reduction index from a (possibly all-reduced) first[];
 // step_tables: also the profile solver's K3 step tables (solve_tab; skipped when the banded
-// solver takes the window).
-void build_profile(BAPlan& plan, const std::vector<int32_t>& first, bool step_tables = true);
+// solver takes the window).  prior_k > 0 (a pose prior over free cameras 0 .. prior_k - 1, whose
+// first[] the caller lowered to 0): every block of the leading prior_k x prior_k triangle gets one
+// more slab row behind its slots (the last of its prof_src_ptr range, prof_src -1) and each of those
+// cameras one more rhs entry (the last of its camb_ptr range, camb_src -1), which nothing of K1
+// writes: ba_prior.hip fills them, and K2 sums them with the rest.  prior_k = 0 changes nothing.
+void build_profile(BAPlan& plan, const std::vector<int32_t>& first, bool step_tables = true, int prior_k = 0);
 // 64-bit FNV-1a over every plan array in a fixed order (vo_ba_plan_digest).
 uint64_t plan_digest(const BAPlan& plan);
 

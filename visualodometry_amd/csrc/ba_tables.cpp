@@ -166,4 +166,23 @@ std::string lm_options(const vo_ba_lm_options* opt, double problem_lambda, vo_ba
   return "";
 }
 
+std::string pose_prior_error(const vo_ba_problem* prob, const vo_ba_pose_prior* pr) {
+  if (!prob || !pr) return "vo_ba_setup_prior: null problem or prior";
+  if (pr->reserved != 0) return "vo_ba_setup_prior: reserved must be 0";
+  if (pr->n_poses < 1) return "vo_ba_setup_prior: a prior covers at least one pose";
+  if (prob->n_fixed < 0 || pr->n_poses > prob->n_poses - prob->n_fixed)
+    return "vo_ba_setup_prior: the prior covers more poses than the window has free";
+  if (!pr->info || !pr->rhs || !pr->poses0) return "vo_ba_setup_prior: null arrays";
+  const size_t n = 6ull * pr->n_poses;
+  if (!std::isfinite(pr->cost0)) return "vo_ba_setup_prior: cost0 is not finite";
+  for (size_t r = 0; r < n; ++r) {
+    if (!std::isfinite(pr->rhs[r])) return "vo_ba_setup_prior: rhs is not finite";
+    for (size_t c = 0; c <= r; ++c)  // (the upper triangle is not read)
+      if (!std::isfinite(pr->info[r * n + c])) return "vo_ba_setup_prior: info is not finite";
+  }
+  for (size_t e = 0; e < 2 * n; ++e)
+    if (!std::isfinite(pr->poses0[e])) return "vo_ba_setup_prior: poses0 is not finite";
+  return "";
+}
+
 }  // namespace vo

@@ -83,4 +83,8 @@ struct LmLog {
 // lambda); returns the message of the first bad field, empty if none.
 std::string lm_options(const vo_ba_lm_options* opt, double problem_lambda, vo_ba_lm_options& o);
 
+// vo_ba_setup_prior's argument checks (vo_hip.h; no device needed): the message of the first bad
+// field of the prior against its problem, empty if none.
+std::string pose_prior_error(const vo_ba_problem* prob, const vo_ba_pose_prior* prior);
+
 }  // namespace vo

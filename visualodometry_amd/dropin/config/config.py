@@ -60,6 +60,9 @@ class VOConfig:
     ba_cull_rounds: int = 0  # 0: off
     ba_cull_chi2: float = 0.0  # deactivate an observation whose weighted squared error (px^2) exceeds this; 0: not tested
     ba_cull_min_depth: float = 0.0  # deactivate an observation at or below this camera-frame depth
+    # marginalisation prior: once the window is full, the oldest keyframe and the landmarks it sees leave as a
+    # quadratic cost on the poses that stay, and one fixed pose fewer holds the gauge (2 -> 1 -> 0)
+    ba_marginalize: bool = False
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)

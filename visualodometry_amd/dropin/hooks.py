@@ -71,9 +71,41 @@ class KeyframeWindow:
         self.n_fixed = int(n_fixed)
         self.max_track = int(max_track)
         self.frames: deque[KeyframeRecord] = deque(maxlen=self.size)
+        # marginalisation (cfg.ba_marginalize, slide()): the prior what left the window handed to
+        # the poses that stay, the landmark ids it absorbed, and the fixed poses of the next window
+        self.prior = None
+        self.marginalised: set = set()
+        self.cur_fixed = self.n_fixed
 
     def reset(self) -> None:
         self.frames.clear()
+        self.clear_prior()
+        self.marginalised.clear()
+
+    def clear_prior(self) -> None:
+        """Back to a window without a prior: the configured fixed poses hold the gauge again.  The
+        absorbed landmarks stay out of the window (their information went with the prior)."""
+        self.prior = None
+        self.cur_fixed = self.n_fixed
+
+    def full(self) -> bool:
+        return len(self.frames) == self.size
+
+    def slide(self, prior, absorbed_ids) -> None:
+        """The oldest keyframe leaves now (the next ``add`` would drop it anyway): ``prior`` is what it
+        and the landmarks ``absorbed_ids`` leave on the poses that stay, which one fixed pose fewer
+        holds from here on.  Those landmarks stay in the map for PnP and leave ``observations``."""
+        self.frames.popleft()
+        self.prior = prior
+        self.marginalised.update(int(i) for i in np.asarray(absorbed_ids).reshape(-1))
+        self.cur_fixed = max(0, self.cur_fixed - 1)
+        # ids no keyframe of the window observes any more have nothing left to be kept out of
+        # (ids are never reused), so the set stays the size of what the window can see
+        seen = [a for fr in self.frames for a in [fr.ids] + fr.extra_ids]
+        if seen:
+            self.marginalised.intersection_update(np.unique(np.concatenate(seen)).tolist())
+        else:
+            self.marginalised.clear()
 
     def add(self, T_wc, uv, ids, prev_uv=None, prev_ids=None) -> None:
         """Append a keyframe; ``prev_uv/prev_ids`` are new observations of the previous keyframe."""
@@ -96,6 +128,8 @@ class KeyframeWindow:
                 keep = map_points.contains(i)
             else:
                 keep = (i >= 0) & np.fromiter((int(x) in map_points for x in i), bool, i.size)
+            if self.marginalised:
+                keep = keep & ~np.isin(i, np.fromiter(self.marginalised, np.int64, len(self.marginalised)))
             kf.append(np.full(int(keep.sum()), k, np.int32))
             uv.append(u[keep])
             pid.append(i[keep])
@@ -105,7 +139,7 @@ class KeyframeWindow:
 
     def build(self, map_points: dict):
         """-> (BAWindow, landmark ids) or (None, None) if the window has nothing to adjust."""
-        if len(self.frames) <= self.n_fixed:
+        if len(self.frames) <= self.cur_fixed:
             return None, None
         kf, uv, pid = self.observations(map_points)
         if pid.size == 0:
@@ -137,7 +171,9 @@ class KeyframeWindow:
             points = np.stack([np.asarray(map_points[int(i)], np.float64).reshape(3) for i in lm_ids])
         poses_cw = np.stack([np.linalg.inv(fr.T_wc) for fr in self.frames])
         w = BAWindow(poses_cw=poses_cw, points=points, obs_uv=uv.astype(np.float32), obs_cam=kf.astype(np.int32),
-                     obs_pt=remap[inv].astype(np.int32), n_fixed=self.n_fixed)
+                     obs_pt=remap[inv].astype(np.int32), n_fixed=self.cur_fixed)
+        if self.prior is not None and self.prior.n_poses <= len(self.frames) - self.cur_fixed:
+            w.prior = self.prior
         return w, lm_ids
 
     def write_back(self, res: BAResult, lm_ids, map_points: dict, obs_pt=None) -> None:
@@ -201,12 +237,28 @@ def run_window_ba(vo, win: KeyframeWindow):
         vo._vo_amd_ba = ba
     # cfg.ba_covariance: the result (kept on vo._vo_amd_last_ba) also carries the pose and landmark
     # covariance of the adjusted window; no policy here reads it
-    res = ba.optimize(window, return_covariance=True) if getattr(cfg, "ba_covariance", False) else ba.optimize(window)
+    # cfg.ba_marginalize: a full window also computes the prior its oldest keyframe leaves behind
+    kw = {}
+    if getattr(cfg, "ba_covariance", False):
+        kw["return_covariance"] = True
+    marg = bool(getattr(cfg, "ba_marginalize", False))  # (off: nothing of the window but build / write_back is used)
+    slide = marg and win.full()
+    if slide:
+        kw["marginalize"] = 1
+    res = ba.optimize(window, **kw)
     if res.status != "ok" or not np.all(np.isfinite(res.cost_per_iter)) or \
             res.cost_per_iter[-1] > res.cost_per_iter[0]:
         print(f"BA: window rejected ({res.status} {res.message})")
+        if marg:  # what the prior was linearised around is no longer trusted
+            win.clear_prior()
+            win.marginalised.clear()
         return res
     win.write_back(res, lm_ids, vo.map_points, window.obs_pt)
+    if slide:
+        if res.prior is not None and res.point_marginalised is not None:
+            win.slide(res.prior, np.asarray(lm_ids)[res.point_marginalised])
+        else:  # the elimination failed: the next window starts without a prior
+            win.clear_prior()
     T_wc = win.frames[-1].T_wc.copy()
     vo.T_wc = T_wc
     vo.keyframe["T_wc"] = T_wc.copy()
