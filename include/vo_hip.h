@@ -438,6 +438,55 @@ int vo_ba_setup_prior(vo_ctx* ctx, const vo_ba_problem* prob, const vo_ba_pose_p
  * rank, or a K1 layout without a weighted form (the observation mask acts as weights). */
 int vo_ba_marginalize(vo_ctx* ctx, uint64_t session, int n_drop, double lambda, int32_t* n_prior_out, double* info_out,
                       double* rhs_out, double* poses0_out, double* cost0_out, uint8_t* point_marg_out);
+/* Pose factors.  vo_ba_setup_factors is vo_ba_setup_prior with a list of 6x6 costs on window cameras:
+ * unary ones (a soft anchor on one pose) and between ones (a relative motion from the front end, an
+ * odometry or IMU increment, a loop constraint inside the window).
+ * n_factors == 0 is vo_ba_setup_prior(prob, prior) itself, and with prior == NULL too it is
+ * vo_ba_setup: the same plan, digests, launches and bits.
+ * Residual.  With T = T_cw, let A = T_i T_j^-1 for a between factor and A = T_i for a unary one
+ * (cam_j == -1), and Z the measurement of A.  The residual is the twist xi = log(A Z^-1), the log
+ * that of the prior (the exp map's own coefficients; rotations below pi).  Every cost the API
+ * reports (vo_ba_run, vo_ba_run_lm costs and trials, vo_ba_gn_step) gains sum xi^T Lambda xi over
+ * the factors.
+ * Linearisation, first order under the solver's update T <- exp(delta^) T (the first-order Jacobian
+ * of the log is taken as the identity, exact at xi = 0, the prior's convention):
+ *   xi' ~ xi + delta_i - G delta_j,   G = Ad(A) = [[R_A, [t_A]x R_A], [0, R_A]] in (rho, phi) order,
+ * G evaluated at the current poses at every linearisation; a unary factor has no delta_j term.
+ * Contributions to the reduced system S dc = b, by free camera:
+ *   S_ii += Lambda,  S_jj += G^T Lambda G,  S_ij (row i, column j) += -Lambda G,
+ *   b_i  += -Lambda xi,  b_j += G^T Lambda xi.
+ * A fixed endpoint contributes nothing to S and b; a factor between two fixed cameras adds its
+ * (constant) cost only.  Several factors on one pair add, in factor order.  Factors are not
+ * robustified, weighted or culled; the problem's lambda and LM's are added as without them.
+ * vo_ba_gn_step's S_out and b_out and vo_ba_covariance include the factors; vo_ba_residuals and
+ * vo_ba_cull do not see them.  Every sum runs in a fixed order (no atomics): two runs from one state
+ * agree bit for bit, and a rejected LM step restores poses and points bit for bit.
+ * Solver.  A between factor on free poses f_i > f_j lowers the profile's first[f_i] to at most f_j:
+ * the banded solver stays while the widened bandwidth fits it (9 blocks), the profile solver takes
+ * over otherwise; factors between consecutive keyframes never widen anything.  A session with
+ * factors runs K1 as a launch of its own and one more kernel between K1 and the solve launch, which
+ * computes the prior's terms too when the session has both.
+ * vo_ba_marginalize: a factor with an endpoint among the dropped cameras 0..n_drop-1 is marginalised
+ * with the landmark terms and the old prior (it enters the masked system and cost0); every other
+ * factor is left out, and the caller passes those on, re-indexed, to the next window's setup.
+ * VO_ERR_ARG (no device needed): n_factors < 0; factors == NULL with n_factors > 0; cam_i outside
+ * 0..n_poses-1; cam_j >= n_poses or < -1; cam_i == cam_j; a non-finite value in meas or in the lower
+ * triangle of info; n_factors > VO_BA_MAX_POSE_FACTORS.  That cap bounds what a setup adds to every
+ * later linearisation: three slab rows and two rhs entries per factor for K2 to sum, and one cost
+ * entry per 256 factors (one workgroup of the factor kernel) that K2, the LM decision and the
+ * cost-only reduction each sum serially -- 16 entries at the cap.  Orthogonality of meas and
+ * definiteness of info are the caller's: an indefinite Lambda surfaces as VO_ERR_NOT_SPD, as ever.
+ * VO_ERR_STATE: a communicator of more than one rank. */
+#define VO_BA_MAX_POSE_FACTORS 4096
+typedef struct {
+  int32_t cam_i;     /* window camera 0 .. n_poses-1 */
+  int32_t cam_j;     /* a second window camera, or -1: a unary factor on cam_i */
+  double meas[12];   /* Z, laid out as a pose of vo_ba_set_state (R row-major, t):
+                        between: the measured T_i T_j^-1;  unary: the measured T_i   (T = T_cw) */
+  double info[36];   /* Lambda, 6x6 row-major in twist order (rho, phi); the lower triangle is read and mirrored */
+} vo_ba_pose_factor;   /* 392 bytes */
+int vo_ba_setup_factors(vo_ctx* ctx, const vo_ba_problem* prob, const vo_ba_pose_prior* prior,
+                        const vo_ba_pose_factor* factors, int32_t n_factors, uint64_t* session_out);
 /* One-call convenience: setup + set_state + run + get_state. */
 int vo_ba_solve(vo_ctx* ctx, const vo_ba_problem* prob, double* poses, double* points,
                 int iters, double* cost_out);

@@ -22,8 +22,8 @@ int vo_ba_testing_no_chain(vo_ctx* ctx, int on);
 /* Whether the context's last vo_ba_run / vo_ba_run_async was chained (*chained 0 / 1) and how
  * many K1 and solve launches its iterations made (*launches: 2 k split, k + 1 chained; the
  * read-out's launches behind the last iteration are not counted; nor is the prior's kernel that a
- * session set up with a pose prior enqueues behind every K1 launch, so such a session
- * reports 2 k for the 3 k kernels of its iterations).  Either pointer may be NULL. */
+ * session set up with a pose prior or pose factors enqueues behind every K1 launch, so such a
+ * session reports 2 k for the 3 k kernels of its iterations).  Either pointer may be NULL. */
 int vo_ba_testing_last_run(vo_ctx* ctx, int* chained, int* launches);
 
 /* Tool switch: replicas of the publish word the chained K1 workgroups poll (1: one word; 8: one

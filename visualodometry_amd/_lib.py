@@ -64,6 +64,11 @@ class BAPosePriorC(C.Structure):
                 ("rhs", C.POINTER(C.c_double)), ("poses0", C.POINTER(C.c_double)), ("cost0", C.c_double)]
 
 
+class BAPoseFactorC(C.Structure):
+    """``vo_ba_pose_factor``: a 6x6 cost on one window camera (``cam_j`` -1) or between two."""
+    _fields_ = [("cam_i", C.c_int32), ("cam_j", C.c_int32), ("meas", C.c_double * 12), ("info", C.c_double * 36)]
+
+
 # vo_ba_lm_stop_info's reasons (VO_BA_LM_*)
 BA_LM_FAILED, BA_LM_RAN_ALL, BA_LM_FTOL, BA_LM_XTOL, BA_LM_REJECTS = -1, 0, 1, 2, 3
 BA_LM_REASONS = {BA_LM_FAILED: "failed", BA_LM_RAN_ALL: "ran_all", BA_LM_FTOL: "ftol", BA_LM_XTOL: "xtol",
@@ -129,6 +134,8 @@ SIGNATURES = {
     "vo_ba_cull": (_I, [_P, C.c_uint64, C.POINTER(BACullOptionsC), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vo_ba_cull_async": (_I, [_P, C.c_uint64, C.POINTER(BACullOptionsC)]),
     "vo_ba_setup_prior": (_I, [_P, C.POINTER(BAProblemC), C.POINTER(BAPosePriorC), C.POINTER(C.c_uint64)]),
+    "vo_ba_setup_factors": (_I, [_P, C.POINTER(BAProblemC), C.POINTER(BAPosePriorC), C.POINTER(BAPoseFactorC), C.c_int32,
+                                 C.POINTER(C.c_uint64)]),
     "vo_ba_marginalize": (_I, [_P, C.c_uint64, _I, _D, _PI32, _PD, _PD, _PD, _PD, C.POINTER(C.c_uint8)]),
     "vo_ba_solve": (_I, [_P, C.POINTER(BAProblemC), _PD, _PD, _I, _PD]),
     "vo_ba_plan_stats": (_I, [_P, _PI64, _I]),

@@ -53,6 +53,13 @@ left a sliding window stays in its cost; the solve honours it in every linearisa
 reported cost (``tests/ba_prior_ref.py`` restates it on the oracle).  ``BASession.marginalize(n)`` /
 ``optimize(..., marginalize=n)`` compute that prior on the device for the window's first ``n``
 cameras (``vo_ba_marginalize``): ``BAResult.prior`` and ``BAResult.point_marginalised``.
+
+Pose factors (off by default): ``BAWindow.factors`` / ``BASession(..., factors=[PoseFactor(...)])`` add
+6x6 costs ``xi^T info xi`` on one camera (``cam_j`` -1: ``xi = log(T_i Z^-1)``) or between two
+(``xi = log(T_i T_j^-1 Z^-1)``), e.g. the front end's relative motion, an odometry increment or a soft
+anchor (``vo_ba_setup_factors``; ``tests/ba_factor_ref.py`` restates them on the oracle).  They enter
+every linearisation, every reported cost and the covariance; ``marginalize`` folds the factors that
+touch a dropped camera into the prior, and the caller passes the others on, re-indexed.
 """
 
 from __future__ import annotations
@@ -62,7 +69,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BACullOptionsC, BALmOptionsC, BALmStopC, BAPosePriorC, BAProblemC, C, VoError, check, ptr
+from ._lib import (BACullOptionsC, BALmOptionsC, BALmStopC, BAPoseFactorC, BAPosePriorC, BAProblemC, C, VoError, check,
+                   ptr)
 
 
 @dataclass
@@ -79,6 +87,18 @@ class PosePrior:
     @property
     def n_poses(self) -> int:
         return int(np.asarray(self.poses0).shape[0])
+
+
+@dataclass
+class PoseFactor:
+    """A 6x6 cost on window cameras (``vo_ba_pose_factor``): ``xi^T info xi`` with
+    ``xi = log(A meas^-1)`` in twist order ``(rho, phi)``; ``A = T_i T_j^-1`` for a between factor,
+    ``A = T_i`` for a unary one (``cam_j`` -1); ``T`` world -> camera."""
+
+    cam_i: int
+    cam_j: int  # a second window camera, or -1
+    meas: np.ndarray  # (4,4) the measured A
+    info: np.ndarray  # (6,6) Lambda, symmetric (the lower triangle is read)
 
 
 @dataclass
@@ -100,6 +120,8 @@ class BAWindow:
     obs_weight: np.ndarray | None = None
     # a quadratic cost on the leading free poses (cameras n_fixed .. n_fixed + K - 1); None: none
     prior: PosePrior | None = None
+    # pose factors on the window's cameras; None: none
+    factors: list | None = None
 
 
 @dataclass
@@ -234,6 +256,21 @@ def _prior_struct(prior: PosePrior):
     return pc, (info, rhs, rt)
 
 
+def _factor_array(factors):
+    """``(vo_ba_pose_factor[n], n)``; shapes are checked here, before the library reads a short array."""
+    factors = list(factors)
+    arr = (BAPoseFactorC * max(1, len(factors)))()
+    for k, f in enumerate(factors):
+        meas = np.asarray(f.meas, dtype=np.float64)
+        info = np.asarray(f.info, dtype=np.float64)
+        if meas.shape != (4, 4) or info.shape != (6, 6):
+            raise ValueError("PoseFactor: meas must be (4,4) and info (6,6)")
+        arr[k].cam_i, arr[k].cam_j = int(f.cam_i), int(f.cam_j)
+        arr[k].meas[:] = poses_to_rt(meas[None])[0].tolist()
+        arr[k].info[:] = info.reshape(-1).tolist()
+    return arr, len(factors)
+
+
 def plan_probe(K, point_ptr, obs_cam, obs_uv, n_poses: int, n_fixed: int = 2,
                target_segments: int = 512) -> dict:
     """Host-only static plan statistics (no device needed): ``vo_ba_plan_probe``."""
@@ -296,7 +333,7 @@ class BASession:
 
     def __init__(self, K, point_ptr, obs_cam, obs_uv, n_poses: int, n_fixed: int = 2,
                  lam: float = 0.0, ctx: _lib.Context | None = None, huber: float = 0.0,
-                 prior: PosePrior | None = None):
+                 prior: PosePrior | None = None, factors=None):
         self.ctx = ctx or _lib.context()
         self.point_ptr = np.ascontiguousarray(point_ptr, dtype=np.int32)
         self.obs_cam = np.ascontiguousarray(obs_cam, dtype=np.int32)
@@ -309,7 +346,14 @@ class BASession:
         self._prob = prob
         sid = C.c_uint64(0)
         self.prior = prior
-        if prior is None:
+        self.factors = list(factors) if factors is not None else None
+        if self.factors:
+            pc, keep = _prior_struct(prior) if prior is not None else (None, None)
+            fa, n = _factor_array(self.factors)
+            check(self.ctx.lib.vo_ba_setup_factors(self.ctx.handle, C.byref(prob), C.byref(pc) if pc is not None else None,
+                                                   fa, n, C.byref(sid)), "vo_ba_setup_factors")
+            del keep, fa  # (the library copied the arrays)
+        elif prior is None:
             check(self.ctx.lib.vo_ba_setup(self.ctx.handle, C.byref(prob), C.byref(sid)), "vo_ba_setup")
         else:
             pc, keep = _prior_struct(prior)
@@ -588,7 +632,7 @@ class SlidingWindowBA:
         err2 = depth = pose_cov = point_cov = sigma2 = new_prior = marg_mask = None
         try:
             sess = BASession(self.K, point_ptr, obs_cam, obs_uv, poses.shape[0], n_fixed, self.lam, ctx,
-                             huber=self.huber, prior=window.prior)
+                             huber=self.huber, prior=window.prior, factors=window.factors)
             sess.set_state(poses, pts)
             if window.obs_weight is not None:
                 w = np.asarray(window.obs_weight, dtype=np.float64).reshape(-1)

@@ -729,6 +729,21 @@ int vo_ba_setup_prior(vo_ctx* ctx, const vo_ba_problem* prob, const vo_ba_pose_p
   });
 }
 
+int vo_ba_setup_factors(vo_ctx* ctx, const vo_ba_problem* prob, const vo_ba_pose_prior* prior,
+                        const vo_ba_pose_factor* factors, int32_t n_factors, uint64_t* session_out) {
+  if (n_factors == 0) return vo_ba_setup_prior(ctx, prob, prior, session_out);
+  return guarded([&] {
+    // the factors' and the prior's own fields first: they need no device (nor a context)
+    std::string bad = vo::pose_factor_error(prob, factors, n_factors);
+    if (bad.empty() && prior) bad = vo::pose_prior_error(prob, prior);
+    VO_REQUIRE(bad.empty(), VO_ERR_ARG, "%s", bad.c_str());
+    vo::bind(ctx);
+    VO_REQUIRE(session_out, VO_ERR_ARG, "vo_ba_setup_factors: null session_out");
+    *session_out = 0;
+    *session_out = vo::ba_setup(ctx, prob, prior, factors, n_factors);
+  });
+}
+
 int vo_ba_set_state(vo_ctx* ctx, uint64_t session, const double* poses, const double* points) {
   return ba_call(ctx, session, [&] { vo::ba_set_state(ctx, poses, points); },
                  poses && points ? nullptr : "vo_ba_set_state: null arrays");

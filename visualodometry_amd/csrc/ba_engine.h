@@ -10,7 +10,8 @@ struct vo_ctx;
 
 namespace vo {
 
-uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p, const vo_ba_pose_prior* prior = nullptr);
+uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p, const vo_ba_pose_prior* prior = nullptr,
+                  const vo_ba_pose_factor* factors = nullptr, int n_factors = 0);
 void ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_fixed);
 void ba_check_session(vo_ctx* ctx, uint64_t session);
 void ba_set_state(vo_ctx* ctx, const double* poses, const double* pts);

@@ -110,7 +110,9 @@ class BAEngine {
   // and fail together, so one rank's bad shard is an error everywhere, not a hang.
   // prior: a pose prior over the leading free poses (vo_ba_setup_prior; its fields checked by the
   // caller, ba_tables.h pose_prior_error), null for none.
-  uint64_t setup(const vo_ba_problem* prob, const vo_ba_pose_prior* prior = nullptr) {
+  // factors: n_factors pose factors (vo_ba_setup_factors; checked by the caller, pose_factor_error).
+  uint64_t setup(const vo_ba_problem* prob, const vo_ba_pose_prior* prior = nullptr,
+                 const vo_ba_pose_factor* factors = nullptr, int n_factors = 0) {
     PLAN_T_START();
     for (int64_t& v : setup_clock().ns) v = 0;
     // the previous setup's chunk-image DMA may still read the page-locked images the
@@ -126,6 +128,8 @@ class BAEngine {
     plan_ok_ = false;
     VO_REQUIRE(!prior || !sharded(), VO_ERR_STATE,
                "vo_ba_setup_prior: not with a communicator of more than one rank");
+    VO_REQUIRE(n_factors <= 0 || !sharded(), VO_ERR_STATE,
+               "vo_ba_setup_factors: not with a communicator of more than one rank");
     if (err.empty()) err = plan_window(*prob, prev_ok);  // sections 1 - 4
     agree_on_plan(err);
     VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_setup: %s", err.c_str());
@@ -139,12 +143,18 @@ class BAEngine {
     VO_REQUIRE(prior_k <= plan_.n_free && prior_lds_bytes(prior_k) <= kPriorLdsMax, VO_ERR_ARG,
                "vo_ba_setup_prior: a prior over %d poses (free poses: %d)", prior_k, plan_.n_free);
     for (int i = 0; i < prior_k; ++i) first[i] = 0;
+    // a between factor couples its two free poses
+    FactorRows fac;
+    if (n_factors > 0) {
+      factor_free_cams(plan_.n_fixed, factors, n_factors, fac);
+      factor_lower_first(fac, first);
+    }
     // banded K3 when the block bandwidth and F fit it (decided on first[], before the
     // profile, whose step tables only the profile solver reads); the profile solver otherwise
     const int F = plan_.n_free;
     band_ = band_split(F, std::vector<int>(first.begin(), first.end()));
     band_on_ = F > 0 && band_supported(F, band_.w, plan_.n_poses);
-    build_profile(plan_, first, !band_on_, prior_k);
+    build_profile(plan_, first, !band_on_, prior_k, n_factors > 0 ? &fac : nullptr);
     PLAN_T(7, "setup: profile");
     prob_ = *prob;
     prob_.point_ptr = nullptr;
@@ -165,9 +175,11 @@ class BAEngine {
     d_pose_[1].reserve(P.n_poses * 96ull);
     d_dc_.reserve(std::max(1, F) * 48ull);
     // (with a prior: its slab rows, rhs entries and cost entry behind K1's, build_profile)
-    d_slab_.reserve(std::max(1, prior_k ? P.prof_src_ptr.back() : P.n_slab_slots()) * 288ull);
-    d_slab_b_.reserve(std::max<size_t>(1, prior_k ? P.camb_ptr.back() : P.segcam_f.size()) * 48ull);
-    d_slab_cost_.reserve((std::max(1, P.n_segments()) + (prior_k ? 1 : 0)) * 8ull);
+    // (pose factors: theirs between K1's and the prior's, one cost entry per factor workgroup)
+    const bool extra = prior_k || n_factors > 0;
+    d_slab_.reserve(std::max(1, extra ? P.prof_src_ptr.back() : P.n_slab_slots()) * 288ull);
+    d_slab_b_.reserve(std::max<size_t>(1, extra ? P.camb_ptr.back() : P.segcam_f.size()) * 48ull);
+    d_slab_cost_.reserve((std::max(1, P.n_segments()) + (prior_k ? 1 : 0) + factor_blocks(std::max(0, n_factors))) * 8ull);
     if (!band_on_) {
       pack.add(P.solve_tab, d_solve_tab_);
       const SolveTableLayout& TL = P.solve_layout;
@@ -199,6 +211,7 @@ class BAEngine {
     sess_ = Session{};  // nothing of the previous problem's settings, lazy tables or LM run
     prior_k_ = 0;
     if (prior_k) upload_prior(*prior);
+    if (n_factors > 0) upload_factors(factors, n_factors, fac);
     session_ = ++g_ba_sessions;
     return session_;
   }
@@ -227,12 +240,52 @@ class BAEngine {
     prior_cost0_ = pr.cost0;
   }
 
-  // The prior's kernel behind a K1 launch (or in its place, in a window without segments): the
-  // prior's slab sources and its cost entry at the poses K1 linearised at.
-  void enqueue_prior(const int* status) {
-    if (!prior_k_) return;
+  // The factors' arrays in one buffer: [Z | Lambda (mirrored), entry e of factor f at e n + f |
+  // cam_i, cam_j | the rows build_profile gave them (ints)].
+  void upload_factors(const vo_ba_pose_factor* fs, int n, const FactorRows& fac) {
+    hipStream_t st = ctx_->stream;
+    std::vector<double> h(48ull * n + (7ull * n + 1) / 2);
+    int32_t* ints = reinterpret_cast<int32_t*>(h.data() + 48ull * n);
+    for (int f = 0; f < n; ++f) {
+      for (int e = 0; e < 12; ++e) h[(size_t)e * n + f] = fs[f].meas[e];
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c <= r; ++c)
+          h[(size_t)(12 + 6 * r + c) * n + f] = h[(size_t)(12 + 6 * c + r) * n + f] = fs[f].info[6 * r + c];
+      ints[f] = fs[f].cam_i;
+      ints[n + f] = fs[f].cam_j;
+    }
+    std::copy(fac.rows.begin(), fac.rows.end(), ints + 2 * (size_t)n);
+    upload(d_factors_, h, st);
+    VO_HIP_CHECK(hipStreamSynchronize(st));  // the host vector ends here
+    sess_.n_factors = n;
+  }
+
+  // The prior's and the pose factors' kernel, one launch for both, behind a K1 launch (or in its
+  // place, in a window without segments): their slab sources and cost entries at the poses K1
+  // linearised at.  n_drop > 0 (marginalize): only the factors that touch a dropped camera.
+  void enqueue_prior(const int* status, int n_drop = 0) {
+    if (!prior_k_ && !sess_.n_factors) return;
+    FactorArgs Fa{};
+    if (sess_.n_factors) {
+      const size_t nf = (size_t)sess_.n_factors;
+      Fa.n = sess_.n_factors;
+      Fa.n_drop = n_drop;
+      Fa.data = d_factors_.as<double>();
+      Fa.cams = reinterpret_cast<const int*>(Fa.data + 48 * nf);
+      Fa.rows = Fa.cams + 2 * nf;
+      Fa.poses = d_pose_[cur_].as<double>();
+      Fa.slab = d_slab_.as<double>();
+      Fa.slab_b = d_slab_b_.as<double>();
+      Fa.cost = d_slab_cost_.as<double>() + std::max(1, plan_.n_segments()) + (prior_k_ ? 1 : 0);
+      Fa.status = status;
+    }
+    PriorArgs A{};
+    if (!prior_k_) {
+      launch_prior(A, Fa, ctx_->stream);
+      VO_HIP_CHECK(hipGetLastError());
+      return;
+    }
     const size_t n = 6ull * prior_k_, nblk = (size_t)prior_k_ * (prior_k_ + 1) / 2;
-    PriorArgs A;
     A.K = prior_k_;
     A.n_fixed = plan_.n_fixed;
     A.stage = prior_staged_ ? 0 : 1;  // Lambda's slab rows: written once, nothing else touches them
@@ -248,11 +301,14 @@ class BAEngine {
     A.slab_b = d_slab_b_.as<double>();
     A.cost = d_slab_cost_.as<double>() + std::max(1, plan_.n_segments());
     A.status = status;
-    launch_prior(A, ctx_->stream);
+    launch_prior(A, Fa, ctx_->stream);
     VO_HIP_CHECK(hipGetLastError());
   }
-  // The cost entries K2, the LM decision and finalize_cost sum: the segments' and the prior's.
-  int cost_entries() const { return std::max(1, plan_.n_segments()) + (prior_k_ ? 1 : 0); }
+  // The cost entries K2, the LM decision and finalize_cost sum: the segments', the prior's and the
+  // pose factors' (one per workgroup of theirs).
+  int cost_entries() const {
+    return std::max(1, plan_.n_segments()) + (prior_k_ ? 1 : 0) + factor_blocks(sess_.n_factors);
+  }
 
   // Pre-sizes what a window of about (n_poses, n_points, n_obs) needs, outside the keyframe
   // calls: both plan objects' host arrays (plan_ and prev_plan_ alternate between setups; the
@@ -549,7 +605,8 @@ class BAEngine {
       VO_REQUIRE(ok, VO_ERR_STATE, "vo_ba_marginalize: no weighted K1 instantiation for this layout");
       VO_HIP_CHECK(hipGetLastError());
     }
-    enqueue_prior(nullptr);  // the session's prior is marginalised in full
+    // the session's prior is marginalised in full, of its pose factors those on a dropped camera
+    enqueue_prior(nullptr, n_drop);
     ReduceArgs Rd = reduce_args();
     Rd.lambda = 0.0;  // the damping goes on the eliminated blocks only (ba_marg_kernel)
     Rd.lm_lambda = nullptr;
@@ -1506,6 +1563,7 @@ class BAEngine {
            (int64_t)nseg * kBandChainChunks == plan_.n_chunks() && nseg + 2 <= ctx_->num_cus && !lm_lambda_ &&
            !sess_.weighted &&  // observation weights: the separate K1 launch (the chained K1 has no weighted form)
            !prior_k_ &&        // a pose prior: its kernel runs between K1 and the solve launch
+           !sess_.n_factors &&  // pose factors: the same kernel
            !ctx_->prof.on && (!stamps_on_ || ctx_->ba_chain_stamps) && !sharded();
   }
 
@@ -1641,6 +1699,7 @@ class BAEngine {
     bool obs_uploaded = false, cov_uploaded = false, wt_tables = false;
     vo_ba_lm_stop lm_stop{};  // the LM runs' termination criteria (all zero: never stop)
     LmRun lm;
+    int n_factors = 0;  // the session's pose factors (setup; their device arrays in d_factors_)
   };
   Session sess_;
   // the session's pose prior (setup): its size (0: none), cost0 and device arrays (upload_prior)
@@ -1648,6 +1707,7 @@ class BAEngine {
   bool prior_staged_ = false;
   double prior_cost0_ = 0.0;
   DevBuf d_prior_;
+  DevBuf d_factors_;
   DevBuf d_marg_;  // marginalize()'s scratch
   // step control (run_lm): the damping's device address while an LM run enqueues its kernels
   // (null otherwise: the GN kernels), the log and the landmark snapshot
@@ -1673,8 +1733,9 @@ BAEngine* ba_engine(vo_ctx* ctx) {
   if (!ctx->ba) ctx->ba.reset(new BAEngine(ctx));
   return ctx->ba.get();
 }
-uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p, const vo_ba_pose_prior* prior) {
-  return ba_engine(ctx)->setup(p, prior);
+uint64_t ba_setup(vo_ctx* ctx, const vo_ba_problem* p, const vo_ba_pose_prior* prior, const vo_ba_pose_factor* factors,
+                  int n_factors) {
+  return ba_engine(ctx)->setup(p, prior, factors, n_factors);
 }
 void ba_reserve(vo_ctx* ctx, int n_poses, int n_points, int64_t n_obs, int n_fixed) {
   ba_engine(ctx)->reserve(n_poses, n_points, n_obs, n_fixed);

@@ -1233,7 +1233,7 @@ std::vector<int32_t> local_profile_first(const BAPlan& P) {
   return first;
 }
 
-void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_tables, int prior_k) {
+void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_tables, int prior_k, FactorRows* fac) {
   const int F = P.n_free;
   P.prof_first = first;
   filled(P.prof_off, F + 1, 0);
@@ -1259,8 +1259,20 @@ void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_table
   size_t nprior = 0;
   for (int i = 0; i < prior_k; ++i)
     for (int j = first[i]; j <= i; ++j, ++nprior) ++P.prof_src_ptr[P.prof_off[i] + (j - first[i]) + 1];
+  // pose factors' sources (fac, in factor order): one more slab row per factor in each block it
+  // touches -- (fi, fi), (fj, fj) and the off-diagonal one of two free cameras -- between the
+  // slots' and the prior's, one more rhs entry per free endpoint likewise (source -1)
+  const size_t nfac = fac ? fac->fi.size() : 0;
+  size_t nfrows = 0, nfcams = 0;
+  auto fblk = [&](int i, int j) { return P.prof_off[i] + (j - first[i]); };
+  for (size_t k = 0; k < nfac; ++k) {
+    const int fi = fac->fi[k], fj = fac->fj[k];
+    if (fi >= 0) ++P.prof_src_ptr[fblk(fi, fi) + 1], ++nfrows, ++nfcams;
+    if (fj >= 0) ++P.prof_src_ptr[fblk(fj, fj) + 1], ++nfrows, ++nfcams;
+    if (fi >= 0 && fj >= 0) ++P.prof_src_ptr[fblk(std::max(fi, fj), std::min(fi, fj)) + 1], ++nfrows;
+  }
   for (int b = 0; b < nb; ++b) P.prof_src_ptr[b + 1] += P.prof_src_ptr[b];
-  if (nprior) filled(P.prof_src, nslot + nprior, -1);
+  if (nprior + nfrows) filled(P.prof_src, nslot + nprior + nfrows, -1);
   else sized(P.prof_src, nslot);
   filled(P.slab_pos, std::max<size_t>(nslot, 1), 0);
   {
@@ -1270,12 +1282,24 @@ void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_table
       P.prof_src[k] = (int32_t)s;
       P.slab_pos[s] = k;
     }
+    if (nfac) fac->rows.assign(5 * nfac, -1);
+    for (size_t k = 0; k < nfac; ++k) {
+      const int fi = fac->fi[k], fj = fac->fj[k];
+      int32_t* r = &fac->rows[5 * k];
+      if (fi >= 0) r[0] = next[fblk(fi, fi)]++;
+      if (fj >= 0) r[1] = next[fblk(fj, fj)]++;
+      if (fi >= 0 && fj >= 0) r[2] = next[fblk(std::max(fi, fj), std::min(fi, fj))]++;
+    }
   }
   filled(P.camb_ptr, F + 1, 0);
   for (size_t e = 0; e < nent; ++e) ++P.camb_ptr[P.segcam_f[e] + 1];
   for (int f = 0; f < prior_k; ++f) ++P.camb_ptr[f + 1];
+  for (size_t k = 0; k < nfac; ++k) {
+    if (fac->fi[k] >= 0) ++P.camb_ptr[fac->fi[k] + 1];
+    if (fac->fj[k] >= 0) ++P.camb_ptr[fac->fj[k] + 1];
+  }
   for (int f = 0; f < F; ++f) P.camb_ptr[f + 1] += P.camb_ptr[f];
-  if (prior_k > 0) filled(P.camb_src, nent + prior_k, -1);
+  if (prior_k > 0 || nfcams) filled(P.camb_src, nent + prior_k + nfcams, -1);
   else sized(P.camb_src, nent);
   filled(P.cam_pos, std::max<size_t>(nent, 1), 0);
   {
@@ -1284,6 +1308,10 @@ void build_profile(BAPlan& P, const std::vector<int32_t>& first, bool step_table
       const int32_t k = next[P.segcam_f[e]]++;
       P.camb_src[k] = (int32_t)e;
       P.cam_pos[e] = k;
+    }
+    for (size_t k = 0; k < nfac; ++k) {
+      if (fac->fi[k] >= 0) fac->rows[5 * k + 3] = next[fac->fi[k]]++;
+      if (fac->fj[k] >= 0) fac->rows[5 * k + 4] = next[fac->fj[k]]++;
     }
   }
   if (P.prof_src.empty()) P.prof_src.push_back(0);

@@ -329,7 +329,18 @@ std::vector<int32_t> local_profile_first(const BAPlan& plan);
 // more slab row behind its slots (the last of its prof_src_ptr range, prof_src -1) and each of those
 // cameras one more rhs entry (the last of its camb_ptr range, camb_src -1), which nothing of K1
 // writes: ba_prior.hip fills them, and K2 sums them with the rest.  prior_k = 0 changes nothing.
-void build_profile(BAPlan& plan, const std::vector<int32_t>& first, bool step_tables = true, int prior_k = 0);
+// fac (pose factors, vo_ba_setup_factors; first[] lowered by the caller, ba_tables.h
+// factor_lower_first): per factor one more slab row in each block it touches and one more rhs entry
+// per free endpoint, in factor order, behind K1's sources and ahead of the prior's; their positions
+// come back in fac->rows.  Null or empty changes nothing.
+struct FactorRows {
+  std::vector<int32_t> fi, fj;  // in: the free-camera index of cam_i / cam_j; -1: fixed, or (fj) a unary factor
+  // out, 5 per factor: the slab rows of blocks (fi, fi), (fj, fj), (max, min) and the rhs rows of
+  // fi and fj; -1: none
+  std::vector<int32_t> rows;
+};
+void build_profile(BAPlan& plan, const std::vector<int32_t>& first, bool step_tables = true, int prior_k = 0,
+                   FactorRows* fac = nullptr);
 // 64-bit FNV-1a over every plan array in a fixed order (vo_ba_plan_digest).
 uint64_t plan_digest(const BAPlan& plan);
 

@@ -14,7 +14,7 @@ namespace vo {
 // triangle, eta - Lambda xi to the extra rhs row of each of its cameras and E to the cost entry
 // behind the segments', and K2 (any form of it) sums them with K1's in its fixed order.
 struct PriorArgs {
-  int K, n_fixed;
+  int K = 0, n_fixed = 0;  // K 0: no prior
   int stage;             // write Lambda's blocks to their slab rows (a session's first launch)
   double cost0;
   const double* info;    // (6K, 6K) Lambda, symmetric (the host mirrored the lower triangle)
@@ -60,8 +60,28 @@ void launch_marg_mask(const MargMaskArgs& A, hipStream_t st);
 void launch_marg_gather(const MargArgs& A, hipStream_t st);
 void launch_marg(const MargArgs& A, hipStream_t st);
 
+// Pose factors (vo_ba_setup_factors, DESIGN.md §Pose factors): factor k's residual is the twist
+// xi = log(A Z^-1), A = T_i T_j^-1 (between) or T_i (unary); it adds xi^T Lambda xi to the cost and,
+// with G = Ad(A), Lambda / G^T Lambda G / -Lambda G to the blocks (i, i) / (j, j) / (i, j) of S and
+// -Lambda xi / G^T Lambda xi to b_i / b_j, as slab sources of its own (ba_plan.h build_profile, fac).
+constexpr int kFactorThreads = 256;  // one lane per factor; one cost entry per workgroup
+struct FactorArgs {
+  int n = 0;           // factors (0: none)
+  int n_drop = 0;      // > 0 (vo_ba_marginalize): factors without a camera among 0 .. n_drop - 1 write zeros
+  const int* cams;     // (2n) cam_i (n) | cam_j (n): window cameras, cam_j -1 for a unary factor
+  const int* rows;     // (5n) per factor: slab rows of (i, i), (j, j), (max, min); rhs rows of i, j; -1: none
+  const double* data;  // (48n) entry e of factor f at e n + f: Z (12, a pose) | Lambda (36, mirrored)
+  const double* poses; // (n_poses, 12) the window's current poses
+  double* slab;
+  double* slab_b;
+  double* cost;        // the factors' entries of slab_cost: one per workgroup
+  const int* status;   // a failed earlier step: nothing is written (may be null)
+};
+inline int factor_blocks(int n) { return (n + kFactorThreads - 1) / kFactorThreads; }
+
 size_t prior_lds_bytes(int K);
 constexpr size_t kPriorLdsMax = 64 * 1024;
-void launch_prior(const PriorArgs& A, hipStream_t st);
+// One launch for both: workgroup 0 the prior's terms (A.K > 0), factor_blocks(F.n) more the factors'.
+void launch_prior(const PriorArgs& A, const FactorArgs& F, hipStream_t st);
 
 }  // namespace vo

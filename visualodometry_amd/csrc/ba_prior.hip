@@ -8,6 +8,11 @@
 //                    first launch only: they do not change) -- and the
 //                    cost term cost0 - 2 eta^T xi + xi^T Lambda xi by lane-strided partial sums and a
 //                    fixed tree.  K2 then adds them in its own fixed order (ba_plan.h build_profile).
+// In the same launch, factor_blocks(n) more workgroups take a session's pose factors
+// (vo_ba_setup_factors, DESIGN.md §Pose factors): one lane per factor forms A = T_i T_j^-1 (or T_i),
+// xi = log(A Z^-1) by the prior's log, G = Ad(A), and writes Lambda, G^T Lambda G, -Lambda G,
+// -Lambda xi and G^T Lambda xi to the factor's own slab and rhs rows; the workgroup's cost
+// sum xi^T Lambda xi by a fixed tree to its own cost entry.
 // Every sum runs in a fixed order; no atomics.  IEEE sqrt, division and atan2: none of this is on a
 // solve's chain.
 #include "ba_prior.h"
@@ -99,8 +104,7 @@ __device__ __forceinline__ void se3_log_rel(const double* T, const double* T0, d
 // LDS, all of it dynamic (prior_lds_bytes is the kernel's whole LDS, which setup holds against the
 // 64 KiB a launch gets without an attribute): xi (6K) | Lambda xi (6K) | the matvec's partial sums
 // (max(6K, kPriorThreads)) | the cost tree (kPriorThreads)
-__global__ __launch_bounds__(kPriorThreads) void ba_prior_kernel(PriorArgs A) {
-  extern __shared__ __attribute__((aligned(16))) double prior_lds[];
+__device__ __forceinline__ void prior_terms(const PriorArgs& A, double* prior_lds) {
   const int K = A.K, n = 6 * K, tid = threadIdx.x;
   const double* __restrict__ info = A.info;
   const double* __restrict__ rhs = A.rhs;
@@ -165,6 +169,118 @@ __global__ __launch_bounds__(kPriorThreads) void ba_prior_kernel(PriorArgs A) {
     __syncthreads();
   }
   if (tid == 0) *A.cost = A.cost0 + cpart[0];
+}
+
+// One lane per factor, everything of it in registers; the workgroup's cost by a fixed tree.
+__device__ __forceinline__ void factor_terms(const FactorArgs& A, int blk, double* cpart) {
+  const int tid = threadIdx.x, f = blk * kFactorThreads + tid, n = A.n;
+  if (A.status && *A.status) return;  // (uniform)
+  double cost = 0.0;
+  if (f < n) {
+    const int ci = A.cams[f], cj = A.cams[n + f];
+    const int* __restrict__ rows = A.rows + 5l * f;
+    const int r_ii = rows[0], r_jj = rows[1], r_ij = rows[2], rb_i = rows[3], rb_j = rows[4];
+    const double* __restrict__ dat = A.data + f;
+    const bool live = A.n_drop <= 0 || ci < A.n_drop || (cj >= 0 && cj < A.n_drop);
+    double Z[12], L[36], T[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) Z[e] = dat[(long)e * n];
+#pragma unroll
+    for (int e = 0; e < 36; ++e) L[e] = live ? dat[(long)(12 + e) * n] : 0.0;
+    const double* Ti = A.poses + 12l * ci;
+    if (cj >= 0) {  // A = T_i T_j^-1 = [R_i R_j^T | t_i - R_A t_j]
+      const double* Tj = A.poses + 12l * cj;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) T[3 * r + c] = Ti[3 * r] * Tj[3 * c] + Ti[3 * r + 1] * Tj[3 * c + 1] + Ti[3 * r + 2] * Tj[3 * c + 2];
+#pragma unroll
+      for (int r = 0; r < 3; ++r) T[9 + r] = Ti[9 + r] - (T[3 * r] * Tj[9] + T[3 * r + 1] * Tj[10] + T[3 * r + 2] * Tj[11]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 12; ++e) T[e] = Ti[e];
+    }
+    double xi[6], lx[6];
+    se3_log_rel(T, Z, xi);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double acc = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc += L[6 * r + c] * xi[c];
+      lx[r] = acc;
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) cost += xi[r] * lx[r];
+    if (!live) cost = 0.0;  // (a residual that is not finite must not reach a sum it is no part of)
+    if (r_ii >= 0) {
+#pragma unroll
+      for (int q = 0; q < 36; ++q) A.slab[36l * r_ii + q] = L[q];
+#pragma unroll
+      for (int r = 0; r < 6; ++r) A.slab_b[6l * rb_i + r] = live ? -lx[r] : 0.0;
+    }
+    if (r_jj >= 0) {
+      // G = Ad(A) = [[R, [t]x R], [0, R]]; LG = Lambda G; G^T LG, its lower triangle mirrored
+      const double X[9] = {0, -T[11], T[10], T[11], 0, -T[9], -T[10], T[9], 0};
+      double G[36];
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          G[6 * r + c] = T[3 * r + c];
+          G[6 * (r + 3) + c + 3] = T[3 * r + c];
+          G[6 * (r + 3) + c] = 0.0;
+          G[6 * r + c + 3] = X[3 * r] * T[c] + X[3 * r + 1] * T[3 + c] + X[3 * r + 2] * T[6 + c];
+        }
+      double LG[36];
+#pragma unroll
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          double acc = 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k) acc += L[6 * r + k] * G[6 * k + c];
+          LG[6 * r + c] = acc;
+        }
+#pragma unroll
+      for (int r = 0; r < 6; ++r) {
+#pragma unroll
+        for (int c = 0; c <= r; ++c) {
+          double acc = 0.0;
+#pragma unroll
+          for (int k = 0; k < 6; ++k) acc += G[6 * k + r] * LG[6 * k + c];
+          A.slab[36l * r_jj + 6 * r + c] = acc;
+          A.slab[36l * r_jj + 6 * c + r] = acc;
+        }
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc += G[6 * k + r] * lx[k];
+        A.slab_b[6l * rb_j + r] = live ? acc : 0.0;
+      }
+      // block (i, j) of S is -Lambda G: stored as the layout has it, rows the later camera's
+      if (r_ij >= 0) {
+        const bool tr = ci < cj;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int c = 0; c < 6; ++c) A.slab[36l * r_ij + (tr ? 6 * c + r : 6 * r + c)] = -LG[6 * r + c];
+      }
+    }
+  }
+  cpart[tid] = cost;
+  __syncthreads();
+  for (int m = kFactorThreads / 2; m > 0; m >>= 1) {
+    if (tid < m) cpart[tid] += cpart[tid + m];
+    __syncthreads();
+  }
+  if (tid == 0) A.cost[blk] = cpart[0];
+}
+
+static_assert(kFactorThreads == kPriorThreads, "one launch: the prior's workgroup and the factors' share a block size");
+__global__ __launch_bounds__(kPriorThreads) void ba_prior_kernel(PriorArgs A, FactorArgs Fa) {
+  extern __shared__ __attribute__((aligned(16))) double prior_lds[];
+  const int pb = A.K > 0 ? 1 : 0;
+  if ((int)blockIdx.x < pb) prior_terms(A, prior_lds);
+  else factor_terms(Fa, blockIdx.x - pb, prior_lds);
 }
 
 // ---- vo_ba_marginalize ---------------------------------------------------------------------
@@ -309,9 +425,11 @@ size_t prior_lds_bytes(int K) {
   return (12ull * K + std::max<size_t>(6ull * K, kPriorThreads) + kPriorThreads) * sizeof(double);
 }
 
-void launch_prior(const PriorArgs& A, hipStream_t st) {
-  if (A.K <= 0) return;
-  hipLaunchKernelGGL(ba_prior_kernel, dim3(1), dim3(kPriorThreads), prior_lds_bytes(A.K), st, A);
+void launch_prior(const PriorArgs& A, const FactorArgs& F, hipStream_t st) {
+  const int grid = (A.K > 0 ? 1 : 0) + factor_blocks(F.n);
+  if (grid <= 0) return;
+  const size_t lds = std::max(A.K > 0 ? prior_lds_bytes(A.K) : 0, F.n > 0 ? kFactorThreads * sizeof(double) : 0);
+  hipLaunchKernelGGL(ba_prior_kernel, dim3(grid), dim3(kPriorThreads), lds, st, A, F);
 }
 
 }  // namespace vo

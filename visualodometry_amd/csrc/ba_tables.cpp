@@ -185,4 +185,43 @@ std::string pose_prior_error(const vo_ba_problem* prob, const vo_ba_pose_prior* 
   return "";
 }
 
+std::string pose_factor_error(const vo_ba_problem* prob, const vo_ba_pose_factor* fs, int n) {
+  if (!prob) return "vo_ba_setup_factors: null problem";
+  if (n < 0) return "vo_ba_setup_factors: n_factors < 0";
+  if (n > 0 && !fs) return "vo_ba_setup_factors: null factors";
+  if (n > VO_BA_MAX_POSE_FACTORS)
+    return "vo_ba_setup_factors: more than " + std::to_string(VO_BA_MAX_POSE_FACTORS) + " factors";
+  for (int k = 0; k < n; ++k) {
+    const vo_ba_pose_factor& f = fs[k];
+    const std::string at = "vo_ba_setup_factors: factor " + std::to_string(k) + ": ";
+    if (f.cam_i < 0 || f.cam_i >= prob->n_poses || f.cam_j >= prob->n_poses) return at + "camera out of range";
+    if (f.cam_j < -1) return at + "cam_j must be a camera or -1";
+    if (f.cam_i == f.cam_j) return at + "cam_i == cam_j";
+    for (double v : f.meas)
+      if (!std::isfinite(v)) return at + "meas is not finite";
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c <= r; ++c)  // (the upper triangle is not read)
+        if (!std::isfinite(f.info[6 * r + c])) return at + "info is not finite";
+  }
+  return "";
+}
+
+void factor_free_cams(int n_fixed, const vo_ba_pose_factor* fs, int n, FactorRows& R) {
+  R.fi.resize(std::max(0, n));
+  R.fj.resize(std::max(0, n));
+  R.rows.clear();
+  for (int k = 0; k < n; ++k) {
+    R.fi[k] = fs[k].cam_i >= n_fixed ? fs[k].cam_i - n_fixed : -1;
+    R.fj[k] = fs[k].cam_j >= n_fixed ? fs[k].cam_j - n_fixed : -1;
+  }
+}
+
+void factor_lower_first(const FactorRows& R, std::vector<int32_t>& first) {
+  for (size_t k = 0; k < R.fi.size(); ++k)
+    if (R.fi[k] >= 0 && R.fj[k] >= 0) {
+      const int hi = std::max(R.fi[k], R.fj[k]), lo = std::min(R.fi[k], R.fj[k]);
+      first[hi] = std::min(first[hi], lo);
+    }
+}
+
 }  // namespace vo

@@ -87,4 +87,18 @@ std::string lm_options(const vo_ba_lm_options* opt, double problem_lambda, vo_ba
 // field of the prior against its problem, empty if none.
 std::string pose_prior_error(const vo_ba_problem* prob, const vo_ba_pose_prior* prior);
 
+// vo_ba_setup_factors' argument checks (vo_hip.h; no device needed): the message of the first bad
+// field of the factor list against its problem, empty if none.
+std::string pose_factor_error(const vo_ba_problem* prob, const vo_ba_pose_factor* factors, int n_factors);
+// The factors' free-camera indices (FactorRows::fi / fj, ba_plan.h build_profile): camera - n_fixed,
+// -1 for a fixed camera and for a unary factor's cam_j.
+void factor_free_cams(int n_fixed, const vo_ba_pose_factor* factors, int n_factors, FactorRows& rows);
+// A between factor on free poses couples them: first[max] drops to at most min.
+void factor_lower_first(const FactorRows& rows, std::vector<int32_t>& first);
+// vo_ba_marginalize's rule: a factor is marginalised iff one of its cameras is among the dropped
+// 0 .. n_drop - 1 (the factor kernel applies the same test on the device).
+inline bool factor_marginalised(int cam_i, int cam_j, int n_drop) {
+  return cam_i < n_drop || (cam_j >= 0 && cam_j < n_drop);
+}
+
 }  // namespace vo

@@ -8,6 +8,13 @@
 //   - reserve_window on fixed sizes, LmLog's layout and decoding, lm_options' defaults.
 // Input (binary): int32 n_poses, n_points, n_obs, n_fixed, seg_obs; point_ptr; obs_cam; obs_uv.
 // Optional argv[2]: seg_chunks (wave plans; default 1).
+// Optional argv[3] "factors" (tests/test_ba_factor_tables.py): the pose factors' host tables instead
+// -- an empty factor list leaves every profile array and the digest as they are; a chain over all
+// cameras with a duplicate pair and a unary factor keeps the bandwidth; one more factor between the
+// first and the last free pose spans F - 1; every factor row lies in its block's (camera's) source
+// range behind K1's sources and ahead of the prior's, none twice; the argument checks and the
+// marginalisation's mask rule.  Prints "factors ok <free poses> <bandwidth> <with the chain> <with
+// the far factor> <factor slab rows>".
 // Prints "ok <free poses> <bandwidth> <layouts checked> <chunks> <chunks taken over>" or the
 // first violation.
 #include <algorithm>
@@ -244,6 +251,174 @@ static bool check_lm_log() {
   return true;
 }
 
+static vo_ba_pose_factor make_factor(int i, int j) {
+  vo_ba_pose_factor f{};
+  f.cam_i = i;
+  f.cam_j = j;
+  for (int k = 0; k < 3; ++k) f.meas[4 * k] = 1.0;
+  for (int k = 0; k < 6; ++k) f.info[7 * k] = 1.0;
+  return f;
+}
+
+static int bandwidth(const std::vector<int32_t>& first) {
+  int w = 0;
+  for (size_t i = 0; i < first.size(); ++i) w = std::max(w, (int)i - first[i]);
+  return w;
+}
+
+// every factor row inside its range, behind K1's sources, ahead of the prior's, none twice
+static bool check_factor_rows(const BAPlan& P, const vo::FactorRows& R, int prior_k) {
+  const int F = P.n_free;
+  std::vector<int> slots(P.n_prof_blocks(), 0), ents(F, 0);
+  for (size_t s = 0; s < P.slot_i.size(); ++s) ++slots[P.prof_off[P.slot_i[s]] + P.slot_j[s] - P.prof_first[P.slot_i[s]]];
+  for (size_t e = 0; e < P.segcam_f.size(); ++e) ++ents[P.segcam_f[e]];
+  std::vector<char> used(P.prof_src_ptr.back(), 0), usedb(P.camb_ptr.back(), 0);
+  if (R.rows.size() != 5 * R.fi.size()) FAIL("factor rows: %zu entries for %zu factors", R.rows.size(), R.fi.size());
+  for (size_t k = 0; k < R.fi.size(); ++k) {
+    const int fi = R.fi[k], fj = R.fj[k], hi = std::max(fi, fj), lo = std::min(fi, fj);
+    const int32_t* r = &R.rows[5 * k];
+    const int want_blk[3][2] = {{fi, fi}, {fj, fj}, {lo >= 0 ? hi : -1, lo}};
+    for (int q = 0; q < 3; ++q) {
+      const int i = want_blk[q][0], j = want_blk[q][1];
+      if ((i < 0 || j < 0) != (r[q] < 0)) FAIL("factor %zu: slab row %d is %d", k, q, r[q]);
+      if (r[q] < 0) continue;
+      if (j < P.prof_first[i]) FAIL("factor %zu: block (%d, %d) outside the profile", k, i, j);
+      const int b = P.prof_off[i] + j - P.prof_first[i];
+      const int last = P.prof_src_ptr[b + 1] - (i < prior_k ? 1 : 0);  // (the prior's row is the block's last)
+      if (r[q] < P.prof_src_ptr[b] + slots[b] || r[q] >= last || used[r[q]]) FAIL("factor %zu: slab row %d at %d", k, q, r[q]);
+      if (P.prof_src[r[q]] != -1) FAIL("factor %zu: slab row %d has a K1 source", k, q);
+      used[r[q]] = 1;
+    }
+    const int cams[2] = {fi, fj};
+    for (int q = 0; q < 2; ++q) {
+      const int f = cams[q], row = r[3 + q];
+      if ((f < 0) != (row < 0)) FAIL("factor %zu: rhs row %d is %d", k, q, row);
+      if (row < 0) continue;
+      const int last = P.camb_ptr[f + 1] - (f < prior_k ? 1 : 0);
+      if (row < P.camb_ptr[f] + ents[f] || row >= last || usedb[row] || P.camb_src[row] != -1) FAIL("factor %zu: rhs row %d at %d", k, q, row);
+      usedb[row] = 1;
+    }
+    // factor order within a block: a later factor on the same pair sits behind an earlier one
+    for (size_t k2 = 0; k2 < k; ++k2)
+      if (R.fi[k2] == fi && R.fj[k2] == fj)
+        for (int q = 0; q < 5; ++q)
+          if (r[q] >= 0 && R.rows[5 * k2 + q] >= r[q]) FAIL("factors %zu and %zu on one pair: rows out of factor order", k2, k);
+  }
+  return true;
+}
+
+static bool check_factor_errors(int N) {
+  vo_ba_problem prob{};
+  prob.n_poses = N;
+  prob.n_fixed = 2;
+  std::vector<vo_ba_pose_factor> fs{make_factor(1, 0), make_factor(2, -1), make_factor(1, N - 1)};
+  auto err = [&](const std::vector<vo_ba_pose_factor>& v, int n) { return vo::pose_factor_error(&prob, v.data(), n); };
+  if (!err(fs, 3).empty() || !err(fs, 0).empty()) FAIL("pose_factor_error: a good list refused: %s", err(fs, 3).c_str());
+  if (err(fs, -1).empty() || vo::pose_factor_error(&prob, nullptr, 2).empty() || vo::pose_factor_error(nullptr, fs.data(), 3).empty())
+    FAIL("pose_factor_error: n < 0, null factors or a null problem accepted");
+  auto bad = [&](auto change) {
+    std::vector<vo_ba_pose_factor> v = fs;
+    change(v);
+    const std::string e = err(v, 3);
+    return !e.empty() && e.find("vo_ba_setup_factors") != std::string::npos;
+  };
+  if (!bad([&](auto& v) { v[0].cam_i = N; }) || !bad([&](auto& v) { v[0].cam_i = -1; }) || !bad([&](auto& v) { v[2].cam_j = N; }) ||
+      !bad([&](auto& v) { v[1].cam_j = -2; }) || !bad([&](auto& v) { v[0].cam_j = 1; }) || !bad([&](auto& v) { v[1].meas[11] = NAN; }) ||
+      !bad([&](auto& v) { v[2].info[6 * 5 + 2] = INFINITY; }))
+    FAIL("pose_factor_error: a bad field accepted");
+  std::vector<vo_ba_pose_factor> v = fs;
+  v[0].info[6 * 2 + 5] = NAN;  // above the diagonal: not read
+  if (!err(v, 3).empty()) FAIL("pose_factor_error: reads the upper triangle");
+  std::vector<vo_ba_pose_factor> many(VO_BA_MAX_POSE_FACTORS + 1, fs[0]);
+  if (!err(many, VO_BA_MAX_POSE_FACTORS).empty() || err(many, VO_BA_MAX_POSE_FACTORS + 1).empty()) FAIL("pose_factor_error: the cap");
+  // the mask rule: an endpoint among cameras 0 .. n_drop - 1
+  if (!vo::factor_marginalised(0, 5, 1) || !vo::factor_marginalised(5, 0, 1) || vo::factor_marginalised(1, 5, 1) ||
+      vo::factor_marginalised(3, -1, 3) || !vo::factor_marginalised(2, -1, 3) || !vo::factor_marginalised(7, 2, 3))
+    FAIL("factor_marginalised");
+  return true;
+}
+
+// The pose factors' host tables over plan P (profile built without factors).
+static bool check_factors(BAPlan& P, int N, int nf) {
+  const int F = P.n_free;
+  const std::vector<int32_t> first0 = vo::local_profile_first(P);
+  const uint64_t digest0 = vo::plan_digest(P);
+  const std::vector<int32_t> src_ptr = P.prof_src_ptr, src = P.prof_src, slab_pos = P.slab_pos, cptr = P.camb_ptr, csrc = P.camb_src,
+                             cpos = P.cam_pos, off = P.prof_off, last = P.prof_last, tab = P.solve_tab;
+  auto same = [&] {
+    return P.prof_src_ptr == src_ptr && P.prof_src == src && P.slab_pos == slab_pos && P.camb_ptr == cptr && P.camb_src == csrc &&
+           P.cam_pos == cpos && P.prof_off == off && P.prof_last == last && P.solve_tab == tab && P.prof_first == first0 &&
+           vo::plan_digest(P) == digest0;
+  };
+  // no factors: nothing moves
+  vo::FactorRows none;
+  vo::factor_free_cams(nf, nullptr, 0, none);
+  std::vector<int32_t> first = first0;
+  vo::factor_lower_first(none, first);
+  vo::build_profile(P, first, true, 0, &none);
+  if (first != first0 || !same() || !none.rows.empty()) FAIL("an empty factor list changes the profile");
+  // the chain over all cameras (fixed-fixed and fixed-free pairs included), a duplicate pair, a unary factor
+  std::vector<vo_ba_pose_factor> fs;
+  for (int c = 0; c + 1 < N; ++c) fs.push_back(make_factor(c + 1, c));
+  if (N >= 2) fs.push_back(make_factor(N - 2, N - 1));  // the last pair again, the other way round
+  fs.push_back(make_factor(N - 1, -1));
+  vo::FactorRows chain;
+  vo::factor_free_cams(nf, fs.data(), (int)fs.size(), chain);
+  for (size_t k = 0; k < fs.size(); ++k)
+    if (chain.fi[k] != (fs[k].cam_i >= nf ? fs[k].cam_i - nf : -1) || chain.fj[k] != (fs[k].cam_j >= nf ? fs[k].cam_j - nf : -1))
+      FAIL("factor_free_cams at factor %zu", k);
+  first = first0;
+  vo::factor_lower_first(chain, first);
+  const int w0 = bandwidth(first0), w_chain = bandwidth(first);
+  for (int i = 1; i < F; ++i)
+    if (first[i] > i - 1) FAIL("the chain leaves first[%d] = %d", i, first[i]);
+  vo::build_profile(P, first, true, 0, &chain);
+  if (!check_factor_rows(P, chain, 0)) return false;
+  {  // K1's sources keep their order (K2's summation order over them), the factors' rows lie between
+    std::vector<int32_t> k1, k1b;
+    for (int32_t v : P.prof_src)
+      if (v >= 0) k1.push_back(v);
+    for (int32_t v : P.camb_src)
+      if (v >= 0) k1b.push_back(v);
+    if (k1 != src || k1b != csrc) FAIL("factors reorder K1's sources");
+    for (size_t s = 0; s < P.slot_i.size(); ++s)
+      if (P.prof_src[P.slab_pos[s]] != (int32_t)s) FAIL("slab_pos of slot %zu", s);
+    for (size_t e = 0; e < P.segcam_f.size(); ++e)
+      if (P.camb_src[P.cam_pos[e]] != (int32_t)e) FAIL("cam_pos of entry %zu", e);
+  }
+  size_t rows = 0, brows = 0;
+  for (size_t e = 0; e < chain.rows.size(); ++e) (e % 5 < 3 ? rows : brows) += chain.rows[e] >= 0;
+  if ((size_t)P.prof_src_ptr.back() != P.slot_i.size() + rows || (size_t)P.camb_ptr.back() != P.segcam_f.size() + brows)
+    FAIL("%d slab rows for %zu slots and %zu factor rows, %d rhs rows for %zu entries and %zu", P.prof_src_ptr.back(),
+         P.slot_i.size(), rows, P.camb_ptr.back(), P.segcam_f.size(), brows);
+  // with a prior over the leading poses as well: its rows stay the last of their ranges
+  const int pk = std::min(3, F);
+  std::vector<int32_t> firstp = first;
+  for (int i = 0; i < pk; ++i) firstp[i] = 0;
+  vo::build_profile(P, firstp, true, pk, &chain);
+  if (!check_factor_rows(P, chain, pk)) return false;
+  // one more factor between the first and the last free pose: the profile's span is F - 1
+  int w_far = w_chain;
+  if (F >= 2) {
+    fs.push_back(make_factor(nf, N - 1));
+    vo::FactorRows far;
+    vo::factor_free_cams(nf, fs.data(), (int)fs.size(), far);
+    first = first0;
+    vo::factor_lower_first(far, first);
+    w_far = bandwidth(first);
+    if (first[F - 1] != 0) FAIL("the far factor leaves first[%d] = %d", F - 1, first[F - 1]);
+    vo::build_profile(P, first, true, 0, &far);
+    if (!check_factor_rows(P, far, 0)) return false;
+    if (!check_layout(P, false, w_far, F, "profile layout with the far factor")) return false;
+  }
+  // and back: the profile without factors again
+  vo::build_profile(P, first0);
+  if (!same()) FAIL("the profile without factors differs after one with factors");
+  if (!check_factor_errors(N)) return false;
+  std::printf("factors ok %d %d %d %d %zu\n", F, w0, w_chain, w_far, rows);
+  return true;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
   FILE* f = std::fopen(argv[1], "rb");
@@ -266,6 +441,7 @@ int main(int argc, char** argv) {
   };
   BAPlan P, P2;
   if (!plan(P, nullptr) || !check_obs(P, ptr, cam, uv)) return 1;
+  if (argc > 3 && std::string(argv[3]) == "factors") return check_factors(P, N, nf) ? 0 : 1;
   const int F = P.n_free;
   int w = 0, layouts = 2;
   for (int i = 0; i < F; ++i) w = std::max(w, i - P.prof_first[i]);

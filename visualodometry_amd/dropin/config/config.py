@@ -63,6 +63,11 @@ class VOConfig:
     # marginalisation prior: once the window is full, the oldest keyframe and the landmarks it sees leave as a
     # quadratic cost on the poses that stay, and one fixed pose fewer holds the gauge (2 -> 1 -> 0)
     ba_marginalize: bool = False
+    # motion factors: the front end's relative pose between consecutive keyframes, as it stood when the newer one
+    # was made, stays in the BA cost as a between factor (it carries the front end's scale)
+    ba_motion_factors: bool = False
+    ba_motion_sigma_t: float = 0.1  # its translation sigma, map units
+    ba_motion_sigma_r: float = 0.02  # its rotation sigma, radians
     sift_on_gpu: bool = True  # SIFT detectAndCompute on the MI355X (frontend.py:27-32,55)
     match_on_gpu: bool = True  # SIFT matching on the MI355X (knn-2 + ratio test)
     match_cross_check: bool = False  # SIFT matching: also require mutual nearest neighbours (one-to-one pairs)

@@ -19,7 +19,9 @@ are the caller's environment):
   :class:`KeyframeWindow` records the new keyframe and, if ``cfg.ba_enabled``,
   runs :class:`~visualodometry_amd.ba.SlidingWindowBA` on the last
   ``cfg.ba_window`` keyframes and writes poses and map points back
-  (SURVEY.md §8a row a11).
+  (SURVEY.md §8a row a11).  With ``cfg.ba_motion_factors`` the window also keeps the front end's
+  relative pose between consecutive keyframes (the motion ``vo.py:152-204`` produced) as between
+  factors of that BA, which otherwise overwrites it.
 
 The reference keeps only the current keyframe's observation of a freshly
 triangulated point (``vo.py:277-284``); the window also records the previous
@@ -34,7 +36,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ..ba import BAResult, BAWindow, SlidingWindowBA
+from ..ba import BAResult, BAWindow, PoseFactor, SlidingWindowBA
 from ..mapstore import MAX_POINTS, MapStore
 
 
@@ -56,6 +58,9 @@ class KeyframeRecord:
     ids: np.ndarray  # (N,) int landmark id per keypoint, -1 if none
     extra_uv: list = field(default_factory=list)  # observations added after the keyframe was made
     extra_ids: list = field(default_factory=list)
+    # motion factors (cfg.ba_motion_factors): the front end's T_cw(previous keyframe) T_cw(this)^-1 as
+    # the two stood when this keyframe was added, before BA; None: not recorded
+    motion: np.ndarray | None = None
 
 
 class KeyframeWindow:
@@ -64,9 +69,21 @@ class KeyframeWindow:
     ``max_track`` caps the observations of one landmark to its most recent
     keyframes: the BA planner handles at most 10 free cameras per landmark
     (DESIGN.md §BA layout).
+
+    ``motion_factors`` (``cfg.ba_motion_factors``, off by default): every keyframe records the front
+    end's relative pose to the one before it, and ``build`` emits one between factor per consecutive
+    pair still in the window, with information ``diag(1/sigma_t^2 x3, 1/sigma_r^2 x3)``.  The record
+    lives on the newer keyframe of a pair, and a pair is emitted only while both are in the window:
+    one whose older keyframe left went into the prior (``cfg.ba_marginalize``) or was dropped.
     """
 
-    def __init__(self, size: int = 50, n_fixed: int = 2, max_track: int = 10):
+    def __init__(self, size: int = 50, n_fixed: int = 2, max_track: int = 10, motion_factors: bool = False,
+                 motion_sigma_t: float = 0.1, motion_sigma_r: float = 0.02):
+        self.motion_factors = bool(motion_factors)
+        if self.motion_factors and not (motion_sigma_t > 0 and motion_sigma_r > 0):
+            raise ValueError("ba_motion_sigma_t and ba_motion_sigma_r must be > 0")
+        self.motion_info = np.diag([1.0 / motion_sigma_t**2] * 3 + [1.0 / motion_sigma_r**2] * 3) \
+            if self.motion_factors else None
         self.size = int(size)
         self.n_fixed = int(n_fixed)
         self.max_track = int(max_track)
@@ -113,8 +130,21 @@ class KeyframeWindow:
             last = self.frames[-1]
             last.extra_uv.append(np.asarray(prev_uv, np.float32).reshape(-1, 2))
             last.extra_ids.append(np.asarray(prev_ids, np.int64))
-        self.frames.append(KeyframeRecord(np.array(T_wc, np.float64), np.asarray(uv, np.float32).reshape(-1, 2),
-                                          np.array(ids, np.int64)))
+        T_wc = np.array(T_wc, np.float64)
+        motion = None
+        if self.motion_factors and self.frames:  # T_cw(prev) T_cw(new)^-1 = T_wc(prev)^-1 T_wc(new)
+            motion = np.linalg.inv(self.frames[-1].T_wc) @ T_wc
+        self.frames.append(KeyframeRecord(T_wc, np.asarray(uv, np.float32).reshape(-1, 2), np.array(ids, np.int64),
+                                          motion=motion))
+
+    def factors(self):
+        """The motion factors of the consecutive pairs in the window (``None`` with the switch off or
+        nothing recorded): between window cameras ``k - 1`` and ``k``, from keyframe ``k``'s record."""
+        if not self.motion_factors:
+            return None
+        out = [PoseFactor(k - 1, k, fr.motion, self.motion_info)
+               for k, fr in enumerate(self.frames) if k > 0 and fr.motion is not None]
+        return out or None
 
     def observations(self, map_points: dict):
         """-> (obs_kf, obs_uv, obs_id) of every window observation of a landmark still in the map."""
@@ -174,6 +204,7 @@ class KeyframeWindow:
                      obs_pt=remap[inv].astype(np.int32), n_fixed=self.cur_fixed)
         if self.prior is not None and self.prior.n_poses <= len(self.frames) - self.cur_fixed:
             w.prior = self.prior
+        w.factors = self.factors()
         return w, lm_ids
 
     def write_back(self, res: BAResult, lm_ids, map_points: dict, obs_pt=None) -> None:
@@ -199,7 +230,10 @@ def _wrap_create_keyframe(orig):
         cfg = self.cfg
         win = getattr(self, "_vo_amd_window", None)
         if win is None:
-            win = KeyframeWindow(getattr(cfg, "ba_window", 50), getattr(cfg, "ba_fixed", 2))
+            win = KeyframeWindow(getattr(cfg, "ba_window", 50), getattr(cfg, "ba_fixed", 2),
+                                 motion_factors=getattr(cfg, "ba_motion_factors", False),
+                                 motion_sigma_t=getattr(cfg, "ba_motion_sigma_t", 0.1),
+                                 motion_sigma_r=getattr(cfg, "ba_motion_sigma_r", 0.02))
             self._vo_amd_window = win
         prev = self.keyframe
         if prev is not None and not win.frames:  # the window starts at the keyframe before the first
