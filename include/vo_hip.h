@@ -143,6 +143,55 @@ int vo_match_mutual(vo_ctx* ctx, const float* des0, int n0, uint64_t des0_tag, c
 int vo_match_mutual_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1,
                                 int batch, int n0, int n1, int dim, double ratio,
                                 int32_t* d_best);
+/* Projection-gated matching (search by projection): query rows (landmarks) against train rows
+ * (the frame's keypoints), each query only among the keypoints inside a window around its
+ * predicted pixel position.  Build-defined: the reference has no such association step.
+ *   Inputs: des0 (n0, dim), opt->pred (n0, 2) and opt->radius (n0, or NULL: opt->radius0 for every
+ *   query) are host arrays; des1 (n1, dim) and opt->kp1 (n1, 2) are host arrays, or with
+ *   VO_MATCH_DEVICE_PTRS in opt->flags device pointers (the feature dict's tensors), validated as
+ *   vo_match_knn2_ratio_dev's (VO_ERR_ARG before any launch).
+ *   Gate: train row j is a candidate of query i iff query i is active and, with the float32
+ *   differences dx = kp1[j].x - pred[i].x, dy = kp1[j].y - pred[i].y,
+ *   (double)dx*dx + (double)dy*dy <= (double)r_i*r_i.  Query i is inactive (no candidates) when
+ *   pred[i] has a non-finite component or !(r_i >= 0) (negative or NaN).  r_i = 0 admits an exactly
+ *   coincident keypoint, r_i = +inf every keypoint with finite coordinates; a keypoint with a
+ *   non-finite coordinate is never a candidate.
+ *   Distance: the float path's arithmetic for every call -- d2 the k-ordered fp32 chain
+ *   acc = fmaf(a_k - b_k, a_k - b_k, acc), dist = sqrtf(d2) correctly rounded (for SIFT integers
+ *   with dim <= 256 the exact integer d2, so the int8 path's values).
+ *   Selection: the two smallest keys (dist, j) among the candidates, equal distances keeping the
+ *   lower j; a candidate whose distance is not < FLT_MAX is never selected.  (i, j1) is kept iff
+ *   query i has a selected candidate, max_dist == 0 or dist1 <= (float)max_dist, and it has only
+ *   one selected candidate or (double)dist1 < ratio * (double)dist2: a lone candidate passes the
+ *   ratio test vacuously (what max_dist is for).
+ *   VO_MATCH_GATE_UNIQUE: among the kept pairs naming the same train row j only the one with the
+ *   smallest key (dist1, i) survives; the output is then one-to-one.
+ *   Output: out_pairs int32 (query, train) in ascending query order, capacity 2*n0 int32;
+ *   out_dist (optional, n0 floats) dist1 per pair; *out_count the number of pairs.  n0 == 0 or
+ *   n1 == 0 gives *out_count = 0.
+ *   VO_ERR_ARG (before the context or a device is touched): opt, out_pairs or out_count NULL,
+ *   negative sizes, dim < 1, a null array with a nonzero size, non-finite or negative ratio or
+ *   max_dist, unknown flag bits, reserved != 0.
+ * width / height are a hint for the extent of the cell grid the keypoints are binned into (0:
+ * unknown).  Results never depend on them, on vo_match_hint, on the query cache or on how the
+ * search is binned: binning only prunes, the gate is evaluated exactly for every pair.
+ * Profiler ids: the clears and the grid build count under 3 (match_pack), the gated search and
+ * the unique filter under 5 (match_f32). */
+#define VO_MATCH_GATE_UNIQUE 2
+typedef struct {
+  const float* pred;    /* (n0, 2) host: predicted pixel position of each query in the train image */
+  const float* radius;  /* (n0) host, or NULL: radius0 for every query */
+  const float* kp1;     /* (n1, 2) keypoint positions of the train rows (host, or device with the flag) */
+  float radius0;
+  int32_t width, height;  /* image extent hint; 0 = unknown */
+  double ratio, max_dist; /* max_dist 0 = not tested */
+  int32_t flags;          /* VO_MATCH_DEVICE_PTRS | VO_MATCH_GATE_UNIQUE */
+  int32_t reserved;       /* must be 0 */
+} vo_match_gate_options;
+int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                   const vo_match_gate_options* opt, int32_t* out_pairs, float* out_dist,
+                   int32_t* out_count);
+
 /* Descriptor-kind hint for this context's later matcher calls (results never depend on
  * it; the device checks every call's values either way):
  *   VO_DESC_AUTO (0, default) launches both paths' kernels; a call runs the one its
@@ -527,6 +576,8 @@ int vo_ba_debug_stamps(vo_ctx* ctx, uint64_t* out, int n);
  *      the first hypotheses of every frame, then the rest for the frames still looping),
  *      20 ess_hyp, 21 ess_score (both: the first slice and the rest), 22 ess_decide,
  *      23 ess_final, 24 ess_pose (essential-matrix initialisation).
+ * vo_match_gated's launches take existing ids: its clears and grid build (count, scan, fill)
+ * count under 3 (match_pack), its gated search and unique filter under 5 (match_f32).
  * vo_ba_run_lm's K1, K2 and K3 launches count under 0, 1 and 2 as vo_ba_run's do; its step
  * decision (ba_lm_decide, which sums the cost partials in K2's order) counts under 1 too: with
  * K2 fused into K3's launch, the default on one rank, it is the only launch there. */

@@ -2,6 +2,7 @@
 #include <cstdarg>
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstring>
 #include <type_traits>
 #include <vector>
@@ -671,6 +672,87 @@ int vo_match_mutual(vo_ctx* ctx, const float* des0, int n0, uint64_t des0_tag, c
       vo::check_device_range(ctx, des1, (size_t)n1 * dim * 4, "des1");
     }
     vo::match_host(ctx, des0, n0, des1, n1, dim, ratio, out_pairs, out_count, nullptr, nullptr, des0_tag, dev, true);
+  });
+}
+
+int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                   const vo_match_gate_options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
+  return guarded([&] {
+    // the arguments' own checks first: they need no device (nor a context)
+    VO_REQUIRE(opt && out_pairs && out_count, VO_ERR_ARG, "vo_match_gated: null options or outputs");
+    VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "vo_match_gated: bad shape n0=%d n1=%d dim=%d", n0, n1,
+               dim);
+    VO_REQUIRE((opt->flags & ~(VO_MATCH_DEVICE_PTRS | VO_MATCH_GATE_UNIQUE)) == 0, VO_ERR_ARG,
+               "vo_match_gated: unknown flags 0x%x", opt->flags);
+    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "vo_match_gated: reserved must be 0");
+    VO_REQUIRE(std::isfinite(opt->ratio) && opt->ratio >= 0.0 && std::isfinite(opt->max_dist) && opt->max_dist >= 0.0,
+               VO_ERR_ARG, "vo_match_gated: ratio and max_dist must be finite and >= 0");
+    VO_REQUIRE((n0 == 0 || (des0 && opt->pred)) && (n1 == 0 || (des1 && opt->kp1)), VO_ERR_ARG,
+               "vo_match_gated: null array with a nonzero size");
+    vo::bind(ctx);
+    const bool dev = (opt->flags & VO_MATCH_DEVICE_PTRS) != 0;
+    if (dev) {  // as vo_match_knn2_ratio_dev: refused before any launch
+      vo::check_device_range(ctx, des1, (size_t)n1 * dim * 4, "des1");
+      vo::check_device_range(ctx, opt->kp1, (size_t)n1 * 8, "kp1");
+    }
+    *out_count = 0;
+    if (n0 == 0 || n1 == 0) return;
+    hipStream_t st = ctx->stream;
+    vo::MatchWorkspace& ws = ctx->match;
+    auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    // descriptors: des0 | des1 (host train rows), each 16-byte aligned for the float4 loads
+    const size_t b0 = a16((size_t)n0 * dim * 4), b1 = (size_t)n1 * dim * 4;
+    ws.des.reserve(b0 + (dev ? 0 : b1) + 16);
+    float* d0 = ws.des.as<float>();
+    const float* d1 = des1;
+    VO_HIP_CHECK(hipMemcpyAsync(d0, des0, (size_t)n0 * dim * 4, hipMemcpyHostToDevice, st));
+    if (!dev) {
+      float* s1 = reinterpret_cast<float*>(ws.des.as<char>() + b0);
+      VO_HIP_CHECK(hipMemcpyAsync(s1, des1, b1, hipMemcpyHostToDevice, st));
+      d1 = s1;
+    }
+    // gate workspace: pred | radius | kp1 (host keypoints) | dist | the grid's scratch
+    const size_t bp = a16((size_t)n0 * 8), br = a16((size_t)n0 * 4), bk = dev ? 0 : a16((size_t)n1 * 8);
+    ws.gate.reserve(bp + br + bk + br + vo::gate_scratch_bytes(n1, opt->width, opt->height));
+    char* gb = ws.gate.as<char>();
+    float* d_pred = reinterpret_cast<float*>(gb);
+    float* d_rad = reinterpret_cast<float*>(gb + bp);
+    float* d_kp = reinterpret_cast<float*>(gb + bp + br);
+    float* d_dist = reinterpret_cast<float*>(gb + bp + br + bk);
+    VO_HIP_CHECK(hipMemcpyAsync(d_pred, opt->pred, (size_t)n0 * 8, hipMemcpyHostToDevice, st));
+    if (opt->radius) VO_HIP_CHECK(hipMemcpyAsync(d_rad, opt->radius, (size_t)n0 * 4, hipMemcpyHostToDevice, st));
+    if (!dev) VO_HIP_CHECK(hipMemcpyAsync(d_kp, opt->kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
+    ws.best.reserve((size_t)n0 * 4);
+    vo::GateArgs g{};
+    g.des0 = d0;
+    g.des1 = d1;
+    g.pred = d_pred;
+    g.radius = opt->radius ? d_rad : nullptr;
+    g.kp1 = dev ? opt->kp1 : d_kp;
+    g.radius0 = opt->radius0;
+    g.n0 = n0;
+    g.n1 = n1;
+    g.dim = dim;
+    g.width = opt->width;
+    g.height = opt->height;
+    g.ratio = opt->ratio;
+    g.max_dist = opt->max_dist;
+    g.unique = (opt->flags & VO_MATCH_GATE_UNIQUE) != 0;
+    g.best = ws.best.as<int32_t>();
+    g.dist = d_dist;
+    vo::gate_run(ctx, g, gb + bp + br + bk + br);
+    ws.pairs.reserve((size_t)n0 * 8 + 16);
+    int32_t* d_pairs = ws.pairs.as<int32_t>();
+    int32_t* d_count = d_pairs + 2 * (size_t)n0;
+    vo::compact_pairs(ctx, g.best, n0, d_pairs, d_count);
+    std::vector<float> dist_q(out_dist ? (size_t)n0 : 0);
+    VO_HIP_CHECK(hipMemcpyAsync(out_count, d_count, 4, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(out_pairs, d_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
+    if (out_dist) VO_HIP_CHECK(hipMemcpyAsync(dist_q.data(), d_dist, (size_t)n0 * 4, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipStreamSynchronize(st));
+    // dist1 per pair: the per-query distances gathered in the pairs' order
+    if (out_dist)
+      for (int m = 0; m < *out_count; ++m) out_dist[m] = dist_q[out_pairs[2 * (size_t)m]];
   });
 }
 

@@ -25,7 +25,8 @@ struct MatchWorkspace {
   DevBuf fpart;     // float path: top-2 of A per (split, row), the sweeps' own split
   DevBuf bmax;      // float path: max |b| per batch entry (zero between calls)
   DevBuf cand;      // float path: candidate lists + counts
-  uint32_t gen = 0;         // generation tag of the current call
+  DevBuf gate;      // gated matcher (match_gate.hip): pred, radius, kp1 staging, cell grid, owner keys, dist
+  uint32_t gen = 0;        // generation tag of the current call
   int kind_hint = 0;        // VO_DESC_* (vo_match_hint)
   bool flag_fresh = true;   // flag not yet zeroed
 };
@@ -163,6 +164,22 @@ void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch
 void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc);
 void compact_pairs(vo_ctx* ctx, const int32_t* d_best, int n0, int32_t* d_pairs,
                    int32_t* d_count);
+// Projection-gated matcher (match_gate.hip): device arrays in, best (n0) and dist (n0) out.
+struct GateArgs {
+  const float* des0;    // (n0, dim)
+  const float* des1;    // (n1, dim)
+  const float* pred;    // (n0, 2)
+  const float* radius;  // (n0) or null: radius0
+  const float* kp1;     // (n1, 2)
+  float radius0;
+  int n0, n1, dim, width, height;
+  double ratio, max_dist;
+  bool unique;
+  int32_t* best;        // (n0) kept train row or -1
+  float* dist;          // (n0) dist1 of the kept pair (unspecified where best is -1)
+};
+size_t gate_scratch_bytes(int n1, int width, int height);
+void gate_run(vo_ctx* ctx, const GateArgs& a, void* scratch);
 // Triangulation entry point (tri.hip): host matrices, device points.
 void tri_run(vo_ctx* ctx, const double* P1, const double* P2, const double* T_cw2, const double* K,
              const float* d_pts1, const float* d_pts2, int n, double min_depth, double max_reproj_err,

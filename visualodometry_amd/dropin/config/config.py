@@ -77,6 +77,14 @@ class VOConfig:
     pnp_on_gpu: bool = True  # cv2.solvePnPRansac of the tracking step on the MI355X
     init_on_gpu: bool = False  # cv2.findEssentialMat + recoverPose of the initialisation on the MI355X
     map_store_arrays: bool = True  # map_points as an id-indexed array store (MapStore)
+    # search by projection: every new keyframe looks for the live map points it did not match, among its
+    # unlabelled keypoints inside a window around each point's projection (matcher.match_gated)
+    map_reobserve: bool = False
+    map_reobserve_radius: float = 15.0  # window radius in pixels (a starting value; nothing measured)
+    map_reobserve_ratio: float = 0.8  # ratio test among the keypoints in the window (likewise untuned)
+    # largest descriptor distance accepted (a lone keypoint in the window passes the ratio test); None: 300 for
+    # SIFT's 0..255 integers, 0.7 for SuperPoint's unit rows (starting values, no accuracy measured)
+    map_reobserve_max_dist: float | None = None
 
 
 # dataset -> (overrides always applied, overrides applied when extractor is SIFT)
@@ -108,8 +116,9 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
     ``src/main.py`` calls ``get_config(dataset)`` only (``main.py:54``), so two
     environment switches reach the back end without touching it:
     ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``), ``VO_AMD_BA=1``
-    (``ba_enabled``), ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``) and ``VO_AMD_INIT=1``
-    (``init_on_gpu``).  Unset, the result equals the reference's.
+    (``ba_enabled``), ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``), ``VO_AMD_INIT=1``
+    (``init_on_gpu``) and ``VO_AMD_REOBSERVE=1`` (``map_reobserve``).  Unset, the result equals
+    the reference's.
     """
     cfg = VOConfig()
     if extractor_type is None:
@@ -120,6 +129,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
         cfg.superpoint_bf_match = True
     if os.environ.get("VO_AMD_INIT", "0") not in ("", "0"):
         cfg.init_on_gpu = True
+    if os.environ.get("VO_AMD_REOBSERVE", "0") not in ("", "0"):
+        cfg.map_reobserve = True
     if extractor_type is not None:
         cfg.extractor_type = extractor_type
     base, sift = _DATASET_OVERRIDES.get(dataset, ({}, {}))

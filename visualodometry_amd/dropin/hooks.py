@@ -21,7 +21,10 @@ are the caller's environment):
   ``cfg.ba_window`` keyframes and writes poses and map points back
   (SURVEY.md §8a row a11).  With ``cfg.ba_motion_factors`` the window also keeps the front end's
   relative pose between consecutive keyframes (the motion ``vo.py:152-204`` produced) as between
-  factors of that BA, which otherwise overwrites it.
+  factors of that BA, which otherwise overwrites it.  With ``cfg.map_reobserve`` (off by default)
+  the new keyframe first looks for the live map points it did not match (:func:`reobserve_map`:
+  search by projection, :func:`visualodometry_amd.matcher.match_gated`), so a landmark that missed
+  one keyframe-to-keyframe match gets its id back instead of a duplicate beside it.
 
 The reference keeps only the current keyframe's observation of a freshly
 triangulated point (``vo.py:277-284``); the window also records the previous
@@ -37,7 +40,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ..ba import BAResult, BAWindow, PoseFactor, SlidingWindowBA
-from ..mapstore import MAX_POINTS, MapStore
+from ..mapstore import MAX_POINTS, LandmarkDescriptors, MapStore
 
 
 def _np(x) -> np.ndarray:
@@ -243,6 +246,8 @@ def _wrap_create_keyframe(orig):
         curr_indices = np.asarray(curr_indices)
         no_id = curr_ids[curr_indices] == -1
         orig(self, curr_feats, curr_ids, ref_indices, curr_indices)
+        if getattr(cfg, "map_reobserve", False):  # (off: no attribute, no call, no array touched)
+            reobserve_map(self, curr_feats, curr_ids, first_new)
         # the previous keyframe saw every newly triangulated point (vo.py:265-284)
         cand = curr_indices[no_id]
         new_ids = curr_ids[cand]
@@ -257,6 +262,75 @@ def _wrap_create_keyframe(orig):
 
     _create_keyframe._vo_amd_wrapped = orig
     return _create_keyframe
+
+
+def _descriptors(feats: dict):
+    d = feats["descriptors"]
+    return d[0] if getattr(d, "ndim", 2) == 3 else d
+
+
+def _rows(a, idx: np.ndarray):
+    """Rows ``idx`` of a numpy array or torch tensor (a tensor stays on its device)."""
+    if hasattr(a, "detach"):
+        import torch
+
+        return a[torch.as_tensor(idx, dtype=torch.long, device=a.device)]
+    return np.asarray(a)[idx]
+
+
+def _image_size(feats: dict, K) -> tuple:
+    """(width, height): the feature dict's ``image_size`` (frontend.py:74), else twice the principal point."""
+    size = feats.get("image_size")
+    if size is not None:
+        w, h = _np(size).reshape(-1)[:2]
+        return int(w), int(h)
+    return int(round(2.0 * K[0, 2])), int(round(2.0 * K[1, 2]))
+
+
+def reobserve_map(vo, curr_feats, curr_ids, first_new: int) -> int:
+    """``cfg.map_reobserve``: after the keyframe's own association, record the descriptors of the
+    landmarks it created (ids ``>= first_new``), then offer every live map point that is not among
+    ``curr_ids``, has a stored descriptor and projects into the image to the keypoints that still
+    have no id, within ``cfg.map_reobserve_radius`` pixels of its projection under ``vo.T_wc``.
+    Matched ids are written into ``curr_ids`` in place (the array the keyframe keeps as ``ids``),
+    one-to-one.  Returns how many."""
+    from .. import matcher
+
+    cfg = vo.cfg
+    store = getattr(vo, "_vo_amd_lm_desc", None)
+    if store is None:
+        store = vo._vo_amd_lm_desc = LandmarkDescriptors()
+    des = _descriptors(curr_feats)
+    new = np.flatnonzero(curr_ids >= first_new)
+    if new.size:
+        store.put(curr_ids[new], _np(_rows(des, new)))
+    mp = vo.map_points
+    if isinstance(mp, MapStore):
+        ids, xyz = mp.arrays()
+    else:
+        ids = np.array(sorted(mp), np.int64)
+        xyz = np.array([np.asarray(mp[int(i)], np.float64).reshape(3) for i in ids]).reshape(-1, 3)
+    free = np.flatnonzero(curr_ids == -1)
+    offer = ~np.isin(ids, curr_ids[curr_ids >= 0]) & store.contains(ids)
+    if not offer.any() or free.size == 0:
+        return 0
+    ids, xyz = ids[offer], xyz[offer]
+    size = _image_size(curr_feats, vo.K)
+    pred, valid = matcher.project_points(xyz, np.linalg.inv(vo.T_wc), vo.K, size, getattr(cfg, "min_depth", 0.0))
+    if not valid.any():
+        return 0
+    ids, pred = ids[valid], pred[valid]  # (a point outside the frame would only be an inactive query)
+    max_dist = getattr(cfg, "map_reobserve_max_dist", None)
+    if max_dist is None:
+        max_dist = 0.7 if getattr(cfg, "extractor_type", "sift") == "superpoint" else 300.0
+    kp = curr_feats["keypoints"]
+    kp = kp[0] if getattr(kp, "ndim", 2) == 3 else kp
+    pairs = matcher.match_gated(store.gather(ids), pred, float(getattr(cfg, "map_reobserve_radius", 15.0)),
+                                _rows(des, free), _rows(kp, free),
+                                ratio=float(getattr(cfg, "map_reobserve_ratio", 0.8)), max_dist=float(max_dist),
+                                unique=True, image_size=size)
+    curr_ids[free[pairs[:, 1]]] = ids[pairs[:, 0]]
+    return len(pairs)
 
 
 def run_window_ba(vo, win: KeyframeWindow):
@@ -331,6 +405,9 @@ def _wrap_prune(orig):
             self.map_points.prune_below(self.next_pt_id - MAX_POINTS)  # vo.py:38-47
         else:
             orig(self)
+        store = getattr(self, "_vo_amd_lm_desc", None)
+        if store is not None:  # cfg.map_reobserve: the descriptors leave with their landmarks
+            store.prune_below(self.next_pt_id - MAX_POINTS)
 
     _prune_map._vo_amd_wrapped = orig
     return _prune_map
@@ -343,6 +420,9 @@ def _wrap_reset(orig):
         win = getattr(self, "_vo_amd_window", None)
         if win is not None:
             win.reset()
+        store = getattr(self, "_vo_amd_lm_desc", None)
+        if store is not None:
+            store.clear()
 
     _reset_system._vo_amd_wrapped = orig
     return _reset_system

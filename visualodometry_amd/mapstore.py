@@ -135,6 +135,59 @@ class MapStore(MutableMapping):
         return ids, self.xyz[ids % self.slots].copy()
 
 
+class LandmarkDescriptors:
+    """Descriptor of the keypoint each landmark was created from (``cfg.map_reobserve``), beside
+    :class:`MapStore` and in its layout: ring slot ``id % slots`` of a float32 ``(slots, dim)``
+    array with the owning id beside it.  ``dim`` is fixed by the first insert.  A slot still held
+    by an older id is overwritten (the map's own prune drops that id first in practice)."""
+
+    def __init__(self, capacity: int = MAX_POINTS, slots: int | None = None):
+        self.capacity = int(capacity)
+        self.slots = int(slots or 2 * self.capacity)
+        self.owner = np.full(self.slots, -1, dtype=np.int64)
+        self.des = None  # (slots, dim) float32 once the first descriptor is in
+        self.dim = None
+
+    def __len__(self) -> int:
+        return int((self.owner >= 0).sum())
+
+    def put(self, ids, des) -> None:
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ids.size == 0:
+            return
+        des = np.asarray(des, dtype=np.float32).reshape(ids.size, -1)
+        if (ids < 0).any():
+            raise KeyError(ids[ids < 0][:5].tolist())
+        if self.des is None:
+            self.dim = des.shape[1]
+            self.des = np.zeros((self.slots, self.dim), dtype=np.float32)
+        elif des.shape[1] != self.dim:
+            raise ValueError(f"descriptor dim {des.shape[1]} differs from the store's {self.dim}")
+        self.owner[ids % self.slots] = ids
+        self.des[ids % self.slots] = des
+
+    def contains(self, ids) -> np.ndarray:
+        ids = np.asarray(ids, dtype=np.int64)
+        ok = ids >= 0
+        return ok & (self.owner[np.where(ok, ids, 0) % self.slots] == ids)
+
+    def gather(self, ids) -> np.ndarray:
+        """(k, dim) float32 descriptors of ``ids`` (KeyError if one is absent)."""
+        ids = np.asarray(ids, dtype=np.int64)
+        if not self.contains(ids).all():
+            raise KeyError(ids[~self.contains(ids)][:5].tolist())
+        return self.des[ids % self.slots].copy()
+
+    def prune_below(self, threshold_id: int) -> int:
+        """Drop every id < ``threshold_id``, as ``MapStore.prune_below``; returns how many."""
+        dead = (self.owner >= 0) & (self.owner < threshold_id)
+        self.owner[dead] = -1
+        return int(dead.sum())
+
+    def clear(self) -> None:
+        self.owner[:] = -1
+
+
 def umeyama(src: np.ndarray, dst: np.ndarray, with_scale: bool = True):
     """Similarity (s, R, t) minimising ||dst - (s R src + t)||^2 over point pairs (n, d)."""
     src = np.asarray(src, dtype=np.float64)

@@ -160,6 +160,116 @@ def _gpu_tensors(des0, des1, ctx):
     return _tensor_2d(des0), _tensor_2d(des1)
 
 
+def _as_xy(p, what: str) -> np.ndarray:
+    if hasattr(p, "detach"):
+        p = p.detach().cpu().numpy()
+    p = np.asarray(p)
+    if p.ndim == 3 and p.shape[0] == 1:  # (1, N, 2) feature-dict layout
+        p = p[0]
+    if p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError(f"{what} must be (N, 2), got shape {p.shape}")
+    return np.ascontiguousarray(p, dtype=np.float32)
+
+
+def match_gated(des0, pred, radius, des1, kp1, ratio: float = RATIO_THRESH, max_dist: float = 0.0,
+                unique: bool = True, image_size=None, return_dist: bool = False,
+                ctx: _lib.Context | None = None):
+    """Projection-gated matching (``vo_match_gated``): query row ``i`` (a landmark's descriptor) is
+    compared only with the train rows whose keypoint ``kp1[j]`` lies within ``radius[i]`` pixels of
+    its predicted position ``pred[i]``; see ``include/vo_hip.h`` for the exact gate and keep rule.
+
+    ``des0 (n0, D)``, ``pred (n0, 2)`` and ``radius`` (a scalar, or ``(n0,)``; negative or NaN = the
+    query is inactive) are host data.  ``des1 (n1, D)`` and ``kp1 (n1, 2)`` may be the feature
+    dict's tensors: torch tensors on the context's GPU are read in place, and the call falls back
+    to host arrays as :func:`match_knn2_ratio` does when the library refuses the pointers.
+    ``max_dist`` 0 is not tested; a lone candidate passes the ratio test, so set it.  ``unique``
+    keeps, per train row, only the pair with the smallest ``(dist, query)``: needed before ids are
+    written.  ``image_size`` ``(width, height)`` only sizes the search grid; results never depend
+    on it.
+
+    Returns ``(M, 2)`` int64 (query, train) pairs in ascending query order, and with
+    ``return_dist`` also their float32 distances."""
+    ctx = ctx or _lib.context()
+    a = _as_des(des0)
+    p = _as_xy(pred, "pred")
+    n0, dim = a.shape
+    if p.shape[0] != n0:
+        raise ValueError(f"pred has {p.shape[0]} rows for {n0} query rows")
+    rad = None
+    radius0 = 0.0
+    if np.ndim(radius) == 0:
+        radius0 = float(radius)
+    else:
+        rad = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if rad.shape[0] != n0:
+            raise ValueError(f"radius has {rad.shape[0]} entries for {n0} query rows")
+    dev = None if getattr(ctx, "_foreign_tensors", False) else _gpu_tensors(des1, kp1, ctx)
+    if dev is not None:
+        b, k = dev
+    else:
+        b, k = _as_des(des1), _as_xy(kp1, "kp1")
+    n1 = b.shape[0]
+    if tuple(k.shape) != (n1, 2):
+        raise ValueError(f"kp1 must be ({n1}, 2), got shape {tuple(k.shape)}")
+    empty = np.empty((0, 2), dtype=np.int64)
+    if n0 == 0 or n1 == 0:
+        return (empty, np.empty(0, np.float32)) if return_dist else empty
+    if dim != b.shape[1]:
+        raise ValueError(f"descriptor dims differ: {dim} vs {b.shape[1]}")
+    width, height = (int(image_size[0]), int(image_size[1])) if image_size is not None else (0, 0)
+    flags = _lib.VO_MATCH_GATE_UNIQUE if unique else 0
+    if dev is not None:
+        import torch
+
+        torch.cuda.current_stream(b.device).synchronize()  # the tensors' producer is done
+        p1, pk = b.data_ptr(), k.data_ptr()
+        flags |= _lib.VO_MATCH_DEVICE_PTRS
+    else:
+        p1, pk = b.ctypes.data, k.ctypes.data
+    opt = _lib.MatchGateOptionsC(pred=p.ctypes.data, radius=rad.ctypes.data if rad is not None else None, kp1=pk,
+                                 radius0=radius0, width=width, height=height, ratio=float(ratio),
+                                 max_dist=float(max_dist), flags=flags, reserved=0)
+    out = np.empty((n0, 2), dtype=np.int32)
+    dist = np.empty(n0, dtype=np.float32)
+    cnt = np.zeros(1, dtype=np.int32)
+    rc = ctx.lib.vo_match_gated(ctx.handle, C.c_void_p(a.ctypes.data), n0, C.c_void_p(p1), n1, dim, C.byref(opt),
+                                ptr(out, C.c_int32), ptr(dist, C.c_float), ptr(cnt, C.c_int32))
+    if dev is not None and rc == _lib.VO_ERR_ARG:
+        # torch's device memory is not this library's HIP runtime's (the library refuses such
+        # pointers before any launch): the host path from here on
+        ctx._foreign_tensors = True
+        return match_gated(a, p, rad if rad is not None else radius0, des1.detach().cpu(), kp1.detach().cpu(), ratio,
+                           max_dist, unique, image_size, return_dist, ctx)
+    check(rc, "vo_match_gated")
+    m = int(cnt[0])
+    pairs = out[:m].astype(np.int64)
+    return (pairs, dist[:m].copy()) if return_dist else pairs
+
+
+def project_points(points_w, T_cw, K, image_size, min_depth: float = 0.0):
+    """Pinhole projection of world points into a frame: ``(pred float32 (n, 2), valid bool (n,))``.
+
+    ``T_cw`` (4, 4) world -> camera, ``K`` (3, 3), ``image_size`` ``(width, height)``.  Computed in
+    numpy float64 and cast once.  A point is invalid when its depth ``z <= min_depth`` or its
+    projection falls outside ``[0, width) x [0, height)`` (or is not finite); the caller gives
+    invalid points radius -1 in :func:`match_gated`."""
+    X = np.asarray(points_w, np.float64).reshape(-1, 3)
+    T = np.asarray(T_cw, np.float64)
+    K = np.asarray(K, np.float64)
+    Xc = X @ T[:3, :3].T + T[:3, 3]
+    z = Xc[:, 2]
+    front = z > float(min_depth)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = K[0, 0] * Xc[:, 0] / z + K[0, 2]
+        v = K[1, 1] * Xc[:, 1] / z + K[1, 2]
+    width, height = float(image_size[0]), float(image_size[1])
+    with np.errstate(invalid="ignore"):
+        valid = front & np.isfinite(u) & np.isfinite(v) & (u >= 0) & (u < width) & (v >= 0) & (v < height)
+    with np.errstate(over="ignore", invalid="ignore"):
+        pred = np.stack([u, v], axis=1).astype(np.float32)
+    return pred, valid
+
+
 def match_knn2(des0, des1, ctx: _lib.Context | None = None):
     """knnMatch(k=2) alone: ``idx (n0, 2) int32`` (-1 = none), ``dist (n0, 2) float32``."""
     a, b = _as_des(des0), _as_des(des1)
