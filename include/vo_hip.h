@@ -192,6 +192,48 @@ int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, in
                    const vo_match_gate_options* opt, int32_t* out_pairs, float* out_dist,
                    int32_t* out_count);
 
+/* Segment-gated matching: vo_match_gated with a capsule for a gate.  Query i is compared only with
+ * the train rows whose keypoint lies within r_i of the segment a_i b_i given in the train image:
+ * dist(kp1[j], segment) <= r_i.  One producer of such segments is the epipolar search for new
+ * landmarks (a keypoint of one view with a depth range is a piece of its epipolar line in the
+ * other: matcher.epipolar_segments); a zero-length segment is vo_match_gated's circular gate with
+ * pred = a, to the bit.  Build-defined: the reference has no such step.
+ *   Everything but the gate is vo_match_gated's contract word for word: the inputs (opt->seg
+ *   (n0, 4) = ax, ay, bx, by and opt->radius are host arrays; des1 and opt->kp1 host, or device
+ *   with VO_MATCH_DEVICE_PTRS and validated alike), the distance, the selection of the two
+ *   smallest (dist, j) with dist < FLT_MAX, the keep rule (max_dist, then the ratio test, vacuous
+ *   for a lone candidate), VO_MATCH_GATE_UNIQUE, the output layout and capacity, count 0 for
+ *   n0 == 0 or n1 == 0, and the VO_ERR_ARG cases, answered before the context or a device is
+ *   touched.
+ *   Gate: query i is active iff its four segment values are finite and r_i >= 0 (not NaN); a
+ *   keypoint with a non-finite coordinate is never a candidate.  With the float32 differences
+ *     dx = bx - ax, dy = by - ay, vx = kx - ax, vy = ky - ay, wx = kx - bx, wy = ky - by
+ *   widened to double (every product of two of them is exact, every two-term sum below is rounded
+ *   once, so fused and unfused evaluation agree to the bit):
+ *     dd = dx*dx + dy*dy, s = vx*dx + vy*dy, cr = vx*dy - vy*dx, r2 = (double)r*r
+ *     if      s <= 0 : candidate iff vx*vx + vy*vy <= r2      (nearest point a)
+ *     else if s >= dd: candidate iff wx*wx + wy*wy <= r2      (nearest point b)
+ *     else           : candidate iff cr*cr <= r2*dd           (the interior; no division)
+ *   in this order, so a == b and r = +inf never form inf * 0; r = +inf admits every keypoint with
+ *   finite coordinates.
+ * width / height size the cell grid only (0: unknown); results never depend on them nor on how
+ * the search walks the grid: binning only prunes, every pair in a walked cell takes the gate above.
+ * Profiler ids as vo_match_gated: the grid build under 3 (match_pack), search and unique filter
+ * under 5 (match_f32). */
+typedef struct {
+  const float* seg;     /* (n0, 4) host: ax, ay, bx, by -- the segment of each query in the train image */
+  const float* radius;  /* (n0) host, or NULL: radius0 for every query */
+  const float* kp1;     /* (n1, 2) host, or device with VO_MATCH_DEVICE_PTRS */
+  float radius0;
+  int32_t width, height;   /* grid extent hint, 0 = unknown; results never depend on it */
+  double ratio, max_dist;  /* max_dist 0 = not tested */
+  int32_t flags;           /* VO_MATCH_DEVICE_PTRS | VO_MATCH_GATE_UNIQUE */
+  int32_t reserved;        /* 0 */
+} vo_match_segment_options;
+int vo_match_segment(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                     const vo_match_segment_options* opt, int32_t* out_pairs, float* out_dist,
+                     int32_t* out_count);
+
 /* Descriptor-kind hint for this context's later matcher calls (results never depend on
  * it; the device checks every call's values either way):
  *   VO_DESC_AUTO (0, default) launches both paths' kernels; a call runs the one its
@@ -577,7 +619,8 @@ int vo_ba_debug_stamps(vo_ctx* ctx, uint64_t* out, int n);
  *      20 ess_hyp, 21 ess_score (both: the first slice and the rest), 22 ess_decide,
  *      23 ess_final, 24 ess_pose (essential-matrix initialisation).
  * vo_match_gated's launches take existing ids: its clears and grid build (count, scan, fill)
- * count under 3 (match_pack), its gated search and unique filter under 5 (match_f32).
+ * count under 3 (match_pack), its gated search and unique filter under 5 (match_f32);
+ * vo_match_segment's count the same way.
  * vo_ba_run_lm's K1, K2 and K3 launches count under 0, 1 and 2 as vo_ba_run's do; its step
  * decision (ba_lm_decide, which sums the cost partials in K2's order) counts under 1 too: with
  * K2 fused into K3's launch, the default on one rank, it is the only launch there. */

@@ -26,8 +26,8 @@ VO_ERR_RCCL = -4
 VO_ERR_NOMEM = -5
 VO_ERR_STATE = -6
 VO_ERR_NODEV = -7
-VO_MATCH_DEVICE_PTRS = 1  # vo_match_mutual / vo_match_gated flags
-VO_MATCH_GATE_UNIQUE = 2  # vo_match_gated: one-to-one output
+VO_MATCH_DEVICE_PTRS = 1  # vo_match_mutual / vo_match_gated / vo_match_segment flags
+VO_MATCH_GATE_UNIQUE = 2  # vo_match_gated / vo_match_segment: one-to-one output
 STATUS_NAMES = {
     VO_OK: "ok", VO_ERR_ARG: "bad argument", VO_ERR_HIP: "HIP error",
     VO_ERR_NOT_SPD: "not positive definite", VO_ERR_RCCL: "RCCL error",
@@ -83,6 +83,13 @@ class MatchGateOptionsC(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MatchSegmentOptionsC(C.Structure):
+    """``vo_match_segment_options``: ``vo_match_gate_options`` with a segment ``(ax, ay, bx, by)`` per query."""
+    _fields_ = [("seg", C.c_void_p), ("radius", C.c_void_p), ("kp1", C.c_void_p), ("radius0", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("ratio", C.c_double), ("max_dist", C.c_double),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BAProblemC(C.Structure):
     _fields_ = [
         ("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32),
@@ -122,6 +129,8 @@ SIGNATURES = {
     "vo_match_mutual": (_I, [_P, C.c_void_p, _I, C.c_uint64, C.c_void_p, _I, _I, _D, _I, _PI32, _PI32]),
     "vo_match_mutual_batch_async": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P]),
     "vo_match_gated": (_I, [_P, C.c_void_p, _I, C.c_void_p, _I, _I, C.POINTER(MatchGateOptionsC), _PI32, _PF, _PI32]),
+    "vo_match_segment": (_I, [_P, C.c_void_p, _I, C.c_void_p, _I, _I, C.POINTER(MatchSegmentOptionsC), _PI32, _PF,
+                               _PI32]),
     "vo_match_hint": (_I, [_P, _I]),
     "vo_ba_setup": (_I, [_P, C.POINTER(BAProblemC), C.POINTER(C.c_uint64)]),
     "vo_ba_set_state": (_I, [_P, C.c_uint64, _PD, _PD]),

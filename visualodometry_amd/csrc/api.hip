@@ -675,20 +675,33 @@ int vo_match_mutual(vo_ctx* ctx, const float* des0, int n0, uint64_t des0_tag, c
   });
 }
 
-int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
-                   const vo_match_gate_options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
+// vo_match_gated and vo_match_segment: one contract but for the gate.  `opt` is either entry's
+// options struct: the two differ in the name and the width of the per-query array (pred: 2 floats,
+// seg: 4), which `gate_of` reads out.
+extern "C++" {
+struct GateOf {
+  const float* query;
+  int qcols;  // 2: predicted position (circular gate); 4: segment a, b (capsule gate)
+};
+static GateOf gate_of(const vo_match_gate_options* o) { return {o->pred, 2}; }
+static GateOf gate_of(const vo_match_segment_options* o) { return {o->seg, 4}; }
+
+template <class Options>
+static int match_gate_entry(const char* fn, vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                            const Options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
   return guarded([&] {
     // the arguments' own checks first: they need no device (nor a context)
-    VO_REQUIRE(opt && out_pairs && out_count, VO_ERR_ARG, "vo_match_gated: null options or outputs");
-    VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "vo_match_gated: bad shape n0=%d n1=%d dim=%d", n0, n1,
-               dim);
+    VO_REQUIRE(opt && out_pairs && out_count, VO_ERR_ARG, "%s: null options or outputs", fn);
+    VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "%s: bad shape n0=%d n1=%d dim=%d", fn, n0, n1, dim);
     VO_REQUIRE((opt->flags & ~(VO_MATCH_DEVICE_PTRS | VO_MATCH_GATE_UNIQUE)) == 0, VO_ERR_ARG,
-               "vo_match_gated: unknown flags 0x%x", opt->flags);
-    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "vo_match_gated: reserved must be 0");
+               "%s: unknown flags 0x%x", fn, opt->flags);
+    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "%s: reserved must be 0", fn);
     VO_REQUIRE(std::isfinite(opt->ratio) && opt->ratio >= 0.0 && std::isfinite(opt->max_dist) && opt->max_dist >= 0.0,
-               VO_ERR_ARG, "vo_match_gated: ratio and max_dist must be finite and >= 0");
-    VO_REQUIRE((n0 == 0 || (des0 && opt->pred)) && (n1 == 0 || (des1 && opt->kp1)), VO_ERR_ARG,
-               "vo_match_gated: null array with a nonzero size");
+               VO_ERR_ARG, "%s: ratio and max_dist must be finite and >= 0", fn);
+    const GateOf gate = gate_of(opt);
+    const size_t qrow = (size_t)gate.qcols * 4;  // bytes per query of the gate's array
+    VO_REQUIRE((n0 == 0 || (des0 && gate.query)) && (n1 == 0 || (des1 && opt->kp1)), VO_ERR_ARG,
+               "%s: null array with a nonzero size", fn);
     vo::bind(ctx);
     const bool dev = (opt->flags & VO_MATCH_DEVICE_PTRS) != 0;
     if (dev) {  // as vo_match_knn2_ratio_dev: refused before any launch
@@ -711,15 +724,15 @@ int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, in
       VO_HIP_CHECK(hipMemcpyAsync(s1, des1, b1, hipMemcpyHostToDevice, st));
       d1 = s1;
     }
-    // gate workspace: pred | radius | kp1 (host keypoints) | dist | the grid's scratch
-    const size_t bp = a16((size_t)n0 * 8), br = a16((size_t)n0 * 4), bk = dev ? 0 : a16((size_t)n1 * 8);
+    // gate workspace: pred or seg | radius | kp1 (host keypoints) | dist | the grid's scratch
+    const size_t bp = a16((size_t)n0 * qrow), br = a16((size_t)n0 * 4), bk = dev ? 0 : a16((size_t)n1 * 8);
     ws.gate.reserve(bp + br + bk + br + vo::gate_scratch_bytes(n1, opt->width, opt->height));
     char* gb = ws.gate.as<char>();
     float* d_pred = reinterpret_cast<float*>(gb);
     float* d_rad = reinterpret_cast<float*>(gb + bp);
     float* d_kp = reinterpret_cast<float*>(gb + bp + br);
     float* d_dist = reinterpret_cast<float*>(gb + bp + br + bk);
-    VO_HIP_CHECK(hipMemcpyAsync(d_pred, opt->pred, (size_t)n0 * 8, hipMemcpyHostToDevice, st));
+    VO_HIP_CHECK(hipMemcpyAsync(d_pred, gate.query, (size_t)n0 * qrow, hipMemcpyHostToDevice, st));
     if (opt->radius) VO_HIP_CHECK(hipMemcpyAsync(d_rad, opt->radius, (size_t)n0 * 4, hipMemcpyHostToDevice, st));
     if (!dev) VO_HIP_CHECK(hipMemcpyAsync(d_kp, opt->kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
     ws.best.reserve((size_t)n0 * 4);
@@ -738,6 +751,7 @@ int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, in
     g.ratio = opt->ratio;
     g.max_dist = opt->max_dist;
     g.unique = (opt->flags & VO_MATCH_GATE_UNIQUE) != 0;
+    g.segment = gate.qcols == 4;
     g.best = ws.best.as<int32_t>();
     g.dist = d_dist;
     vo::gate_run(ctx, g, gb + bp + br + bk + br);
@@ -754,6 +768,17 @@ int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, in
     if (out_dist)
       for (int m = 0; m < *out_count; ++m) out_dist[m] = dist_q[out_pairs[2 * (size_t)m]];
   });
+}
+}  // extern "C++"
+
+int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                   const vo_match_gate_options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
+  return match_gate_entry("vo_match_gated", ctx, des0, n0, des1, n1, dim, opt, out_pairs, out_dist, out_count);
+}
+
+int vo_match_segment(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                     const vo_match_segment_options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
+  return match_gate_entry("vo_match_segment", ctx, des0, n0, des1, n1, dim, opt, out_pairs, out_dist, out_count);
 }
 
 int vo_match_mutual_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0, int n1,

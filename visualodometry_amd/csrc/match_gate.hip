@@ -30,6 +30,19 @@
 // A very large radius stays correct (the range is the whole grid) and is not meant to be fast.
 // Profiler ids: the clears and the grid build count under match_pack (3), search and filter under
 // match_f32 (5).
+//
+// Segment-gated matcher (vo_match_segment): the same grid, claims, filter and compaction; the gate
+// is a capsule, dist(keypoint, segment a_i b_i) <= r_i, evaluated exactly as the header states
+// (float32 differences widened to double, every two-term sum rounded once, no division; a == b is
+// the circular gate above to the bit).  The walk is per grid row: a candidate lies within R of some
+// point p of the segment (R = r plus a margin for the float32 differences), so a keypoint of row cy
+// has p.y inside the row's y band widened by R, and its x within R of that sub-segment's x extent.
+// Row 0 and the last row hold every keypoint clamped into them, so their bands are unbounded on
+// the outer side; the column range is clamped by cell_index like the circular gate's.  A row whose
+// widened band the segment does not reach is skipped.  R not finite (r = +inf, overflowing
+// differences): the whole grid.  The 16 lanes of a query take 16 rows at a time, one each, and
+// then stride over the rows' item ranges laid end to end, so a long thin capsule costs a few
+// trips and not one dependent load chain per row.
 #include <algorithm>
 #include <cfloat>
 
@@ -139,7 +152,7 @@ __global__ __launch_bounds__(256) void gate_fill_kernel(const float* __restrict_
 struct SearchArgs {
   const float* des0;
   const float* des1;
-  const float* pred;
+  const float* pred;  // (n0, 2) circular gate; (n0, 4) a, b for the segment gate
   const float* radius;
   const float* kp1;
   const int32_t* start;
@@ -181,6 +194,24 @@ __device__ __forceinline__ float chain_d2(const float* __restrict__ a, const flo
   return acc;
 }
 
+// The group's top-2, the keep rule, and the claim of the train row (every lane of the wave calls it).
+__device__ __forceinline__ void keep_and_claim(const SearchArgs& p, int i, int gl, uint64_t k1, uint64_t k2) {
+#pragma unroll
+  for (int m = 1; m < kGroup; m <<= 1) merge2(k1, k2, shfl_xor64(k1, m), shfl_xor64(k2, m));
+  if (gl != 0 || i >= p.n0) return;
+  int j1 = -1;
+  float s1 = 0.0f;
+  if (k1 != ~0ull) {
+    s1 = __uint_as_float((uint32_t)(k1 >> 32));
+    const bool near = !p.use_max || s1 <= p.max_dist;
+    const bool distinct = k2 == ~0ull || (double)s1 < p.ratio * (double)__uint_as_float((uint32_t)(k2 >> 32));
+    if (near && distinct) j1 = (int)(uint32_t)k1;
+  }
+  p.best[i] = j1;
+  p.dist[i] = s1;
+  if (p.owner && j1 >= 0) atomicMax(&p.owner[j1], (unsigned long long)~key64(__float_as_uint(s1), (uint32_t)i));
+}
+
 template <bool V4>
 __global__ __launch_bounds__(kSearchThreads) void gate_search_kernel(SearchArgs p) {
   const int i = blockIdx.x * (kSearchThreads / kGroup) + (threadIdx.x / kGroup);
@@ -217,20 +248,121 @@ __global__ __launch_bounds__(kSearchThreads) void gate_search_kernel(SearchArgs 
       }
     }
   }
-#pragma unroll
-  for (int m = 1; m < kGroup; m <<= 1) merge2(k1, k2, shfl_xor64(k1, m), shfl_xor64(k2, m));
-  if (gl != 0 || i >= p.n0) return;
-  int j1 = -1;
-  float s1 = 0.0f;
-  if (k1 != ~0ull) {
-    s1 = __uint_as_float((uint32_t)(k1 >> 32));
-    const bool near = !p.use_max || s1 <= p.max_dist;
-    const bool distinct = k2 == ~0ull || (double)s1 < p.ratio * (double)__uint_as_float((uint32_t)(k2 >> 32));
-    if (near && distinct) j1 = (int)(uint32_t)k1;
+  keep_and_claim(p, i, gl, k1, k2);
+}
+
+// ---- the segment-gated search ---------------------------------------------------
+// The capsule gate of the header, to the letter: float32 differences widened to double, products
+// of two widened floats exact, each two-term sum one rounding (the explicit fma rounds the exact
+// sum once, as the plain form does), the tests in this order.
+struct SegQuery {
+  float ax, ay, bx, by;
+  double dx, dy, dd, r2;
+};
+
+__device__ __forceinline__ bool capsule_gate(const SegQuery& q, float kx, float ky) {
+  const double vx = (double)(kx - q.ax), vy = (double)(ky - q.ay);
+  const double s = fma(vx, q.dx, vy * q.dy);
+  if (s <= 0.0) return fma(vx, vx, vy * vy) <= q.r2;
+  if (s >= q.dd) {
+    const double wx = (double)(kx - q.bx), wy = (double)(ky - q.by);
+    return fma(wx, wx, wy * wy) <= q.r2;
   }
-  p.best[i] = j1;
-  p.dist[i] = s1;
-  if (p.owner && j1 >= 0) atomicMax(&p.owner[j1], (unsigned long long)~key64(__float_as_uint(s1), (uint32_t)i));
+  const double cr = fma(vx, q.dy, -(vy * q.dx));
+  return cr * cr <= q.r2 * q.dd;
+}
+
+template <bool V4>
+__global__ __launch_bounds__(kSearchThreads) void segment_search_kernel(SearchArgs p) {
+  const int i = blockIdx.x * (kSearchThreads / kGroup) + (threadIdx.x / kGroup);
+  const int gl = threadIdx.x & (kGroup - 1);
+  SegQuery q{};
+  float r = -1.0f;
+  if (i < p.n0) {
+    q.ax = p.pred[4 * (long)i];
+    q.ay = p.pred[4 * (long)i + 1];
+    q.bx = p.pred[4 * (long)i + 2];
+    q.by = p.pred[4 * (long)i + 3];
+    r = p.radius ? p.radius[i] : p.radius0;
+  }
+  const bool active = i < p.n0 && finite2(q.ax, q.ay) && finite2(q.bx, q.by) && r >= 0.0f;
+  uint64_t k1 = ~0ull, k2 = ~0ull;
+  if (active) {
+    q.dx = (double)(q.bx - q.ax);
+    q.dy = (double)(q.by - q.ay);
+    q.dd = fma(q.dx, q.dx, q.dy * q.dy);
+    q.r2 = (double)r * (double)r;
+    // The walk works on the exact segment (the float coordinates in double).  An accepted keypoint
+    // is within r (1 + 2^-21) + 2^-21 (L + r) of it, L = |b - a|_1: each float32 difference is off
+    // by at most 2^-24 of itself, so the cross product by at most 2^-22 |v| |d| and a misjudged
+    // end by as much along the segment, with |v| <= |d| + dist.  R takes 1e-5 of both instead.
+    const double ax = q.ax, ay = q.ay, bx = q.bx, by = q.by;
+    const double ex = bx - ax, ey = by - ay;  // exact or, past 2^53 apart, as good as
+    const double R = (double)r + 1e-5 * ((double)r + fabs(ex) + fabs(ey));
+    const bool whole = !(R < 1e30);  // +inf or NaN: no pruning
+    const double cell = 1.0 / p.g.inv_cell;
+    const int gw = p.g.gw, gh = p.g.gh;
+    const int cy0 = whole ? 0 : cell_index(fmin(ay, by) - R, p.g.inv_cell, gh);
+    const int cy1 = whole ? gh - 1 : cell_index(fmax(ay, by) + R, p.g.inv_cell, gh);
+    const float* a = p.des0 + (long)i * p.dim;
+    // A long segment crosses many rows with a few items in each, and a loop over the rows would
+    // pay a dependent start -> items -> keypoint load chain per row.  So each lane of the group
+    // takes one row (16 rows per trip), the lanes' item ranges are laid end to end by a prefix
+    // sum, and the group strides over that one list.  `active`, the row bounds and `total` are
+    // the same in all 16 lanes, so the width-16 shuffles only ever read lanes that run with them.
+    for (int base = cy0; base <= cy1; base += kGroup) {
+      const int cy = base + gl;
+      int t_lo = 0, cnt = 0;  // this lane's row: items [t_lo, t_lo + cnt)
+      if (cy <= cy1) {
+        int cx0 = 0, cx1 = gw - 1;
+        bool reach = true;
+        if (!whole) {
+          // the keypoints of this row have y in [lo, hi): unbounded outwards in the border rows
+          const double lo = cy == 0 ? -INFINITY : (double)cy * cell;
+          const double hi = cy == gh - 1 ? INFINITY : (double)(cy + 1) * cell;
+          double t0 = 0.0, t1 = 1.0;  // the part of the segment with y in [lo - R, hi + R]
+          if (ey != 0.0) {
+            const double ta = ((lo - R) - ay) / ey, tb = ((hi + R) - ay) / ey;
+            t0 = fmax(fmin(ta, tb), 0.0);
+            t1 = fmin(fmax(ta, tb), 1.0);
+          }
+          reach = t0 <= t1;  // else the capsule does not touch this row
+          const double xa = ax + t0 * ex, xb = ax + t1 * ex;
+          cx0 = cell_index(fmin(xa, xb) - R, p.g.inv_cell, gw);
+          cx1 = cell_index(fmax(xa, xb) + R, p.g.inv_cell, gw);
+        }
+        if (reach) {
+          t_lo = p.start[cy * gw + cx0];
+          cnt = p.start[cy * gw + cx1 + 1] - t_lo;
+        }
+      }
+      int end = cnt;  // inclusive prefix sum over the group's lanes
+#pragma unroll
+      for (int d = 1; d < kGroup; d <<= 1) {
+        const int v = __shfl_up(end, d, kGroup);
+        if (gl >= d) end += v;
+      }
+      const int total = __shfl(end, kGroup - 1, kGroup);
+      const int first = end - cnt;
+      for (int b = 0; b < total; b += kGroup) {
+        const int idx = b + gl;
+        int t = -1;  // the idx-th item of the rows laid end to end
+#pragma unroll
+        for (int m = 0; m < kGroup; ++m) {
+          const int f = __shfl(first, m, kGroup), c = __shfl(cnt, m, kGroup), tl = __shfl(t_lo, m, kGroup);
+          if (idx >= f && idx < f + c) t = tl + (idx - f);
+        }
+        if (t >= 0) {
+          const int j = p.items[t];
+          if (capsule_gate(q, p.kp1[2 * (long)j], p.kp1[2 * (long)j + 1])) {
+            const float d = sqrtf_rn(chain_d2<V4>(a, p.des1 + (long)j * p.dim, p.dim));
+            if (d < FLT_MAX) merge2(k1, k2, key64(__float_as_uint(d), (uint32_t)j), ~0ull);
+          }
+        }
+      }
+    }
+  }
+  keep_and_claim(p, i, gl, k1, k2);
 }
 
 // VO_MATCH_GATE_UNIQUE: a kept pair survives iff its query holds the train row's smallest key.
@@ -301,8 +433,13 @@ void gate_run(vo_ctx* ctx, const GateArgs& a, void* scratch) {
   const bool v4 = a.dim % 4 == 0 && (((uintptr_t)a.des0 | (uintptr_t)a.des1) & 15) == 0;
   ctx->prof.begin(st, kKMatchF32);
   const dim3 grid(ceil_div(a.n0, kSearchThreads / kGroup));
-  if (v4) hipLaunchKernelGGL(gate_search_kernel<true>, grid, dim3(kSearchThreads), 0, st, s);
-  else hipLaunchKernelGGL(gate_search_kernel<false>, grid, dim3(kSearchThreads), 0, st, s);
+  if (a.segment) {
+    if (v4) hipLaunchKernelGGL(segment_search_kernel<true>, grid, dim3(kSearchThreads), 0, st, s);
+    else hipLaunchKernelGGL(segment_search_kernel<false>, grid, dim3(kSearchThreads), 0, st, s);
+  } else {
+    if (v4) hipLaunchKernelGGL(gate_search_kernel<true>, grid, dim3(kSearchThreads), 0, st, s);
+    else hipLaunchKernelGGL(gate_search_kernel<false>, grid, dim3(kSearchThreads), 0, st, s);
+  }
   if (s.owner) hipLaunchKernelGGL(gate_unique_kernel, dim3(ceil_div(a.n0, 256)), dim3(256), 0, st, a.best, owner, a.n0);
   VO_HIP_CHECK(hipGetLastError());
   ctx->prof.end(st);

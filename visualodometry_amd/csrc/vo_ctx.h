@@ -164,17 +164,18 @@ void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch
 void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc);
 void compact_pairs(vo_ctx* ctx, const int32_t* d_best, int n0, int32_t* d_pairs,
                    int32_t* d_count);
-// Projection-gated matcher (match_gate.hip): device arrays in, best (n0) and dist (n0) out.
+// Projection-gated and segment-gated matcher (match_gate.hip): device arrays in, best (n0) and dist (n0) out.
 struct GateArgs {
   const float* des0;    // (n0, dim)
   const float* des1;    // (n1, dim)
-  const float* pred;    // (n0, 2)
+  const float* pred;    // (n0, 2); with segment (n0, 4): ax, ay, bx, by
   const float* radius;  // (n0) or null: radius0
   const float* kp1;     // (n1, 2)
   float radius0;
   int n0, n1, dim, width, height;
   double ratio, max_dist;
   bool unique;
+  bool segment;         // the capsule gate of vo_match_segment around pred's segments
   int32_t* best;        // (n0) kept train row or -1
   float* dist;          // (n0) dist1 of the kept pair (unspecified where best is -1)
 };

@@ -85,6 +85,19 @@ class VOConfig:
     # largest descriptor distance accepted (a lone keypoint in the window passes the ratio test); None: 300 for
     # SIFT's 0..255 integers, 0.7 for SuperPoint's unit rows (starting values, no accuracy measured)
     map_reobserve_max_dist: float | None = None
+    # epipolar search for new landmarks: at every new keyframe, the keypoints of the previous keyframe that
+    # the ratio-test match left without a partner are looked for along their epipolar segment in the new one,
+    # among its keypoints that have no id and no partner either (matcher.match_segment), and the pairs are
+    # triangulated like the keyframe's own.  All values below are untuned starting values; no accuracy claimed.
+    map_epipolar_search: bool = False
+    map_epipolar_radius: float = 2.0  # distance in pixels a keypoint may lie from the segment
+    map_epipolar_ratio: float = 0.8  # ratio test among the keypoints along the segment
+    # largest descriptor distance accepted; None: 300 for SIFT's 0..255 integers, 0.7 for SuperPoint's unit rows
+    map_epipolar_max_dist: float | None = None
+    map_epipolar_min_depth: float = 1.0  # depth range searched, in the previous keyframe's camera ...
+    map_epipolar_max_depth: float = 0.0  # ... 0 = up to infinity (the segment ends at the vanishing point)
+    # a keypoint whose clipped segment is shorter has no observable depth from this pair: not searched
+    map_epipolar_min_length: float = 8.0
 
 
 # dataset -> (overrides always applied, overrides applied when extractor is SIFT)
@@ -117,8 +130,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
     environment switches reach the back end without touching it:
     ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``), ``VO_AMD_BA=1``
     (``ba_enabled``), ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``), ``VO_AMD_INIT=1``
-    (``init_on_gpu``) and ``VO_AMD_REOBSERVE=1`` (``map_reobserve``).  Unset, the result equals
-    the reference's.
+    (``init_on_gpu``), ``VO_AMD_REOBSERVE=1`` (``map_reobserve``) and ``VO_AMD_EPIPOLAR=1``
+    (``map_epipolar_search``).  Unset, the result equals the reference's.
     """
     cfg = VOConfig()
     if extractor_type is None:
@@ -131,6 +144,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
         cfg.init_on_gpu = True
     if os.environ.get("VO_AMD_REOBSERVE", "0") not in ("", "0"):
         cfg.map_reobserve = True
+    if os.environ.get("VO_AMD_EPIPOLAR", "0") not in ("", "0"):
+        cfg.map_epipolar_search = True
     if extractor_type is not None:
         cfg.extractor_type = extractor_type
     base, sift = _DATASET_OVERRIDES.get(dataset, ({}, {}))

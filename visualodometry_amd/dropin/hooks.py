@@ -24,7 +24,10 @@ are the caller's environment):
   factors of that BA, which otherwise overwrites it.  With ``cfg.map_reobserve`` (off by default)
   the new keyframe first looks for the live map points it did not match (:func:`reobserve_map`:
   search by projection, :func:`visualodometry_amd.matcher.match_gated`), so a landmark that missed
-  one keyframe-to-keyframe match gets its id back instead of a duplicate beside it.
+  one keyframe-to-keyframe match gets its id back instead of a duplicate beside it.  With
+  ``cfg.map_epipolar_search`` (off by default) the keypoints that match left without a partner are
+  then looked for along their epipolar segments (:func:`epipolar_search`,
+  :func:`visualodometry_amd.matcher.match_segment`) and the pairs triangulated into new landmarks.
 
 The reference keeps only the current keyframe's observation of a freshly
 triangulated point (``vo.py:277-284``); the window also records the previous
@@ -248,6 +251,9 @@ def _wrap_create_keyframe(orig):
         orig(self, curr_feats, curr_ids, ref_indices, curr_indices)
         if getattr(cfg, "map_reobserve", False):  # (off: no attribute, no call, no array touched)
             reobserve_map(self, curr_feats, curr_ids, first_new)
+        found = None
+        if getattr(cfg, "map_epipolar_search", False) and prev is not None:  # (off: as map_reobserve)
+            found = epipolar_search(self, prev, curr_feats, curr_ids, ref_indices, curr_indices)
         # the previous keyframe saw every newly triangulated point (vo.py:265-284)
         cand = curr_indices[no_id]
         new_ids = curr_ids[cand]
@@ -256,7 +262,11 @@ def _wrap_create_keyframe(orig):
         uniq, cnt = np.unique(cand, return_counts=True)
         is_new = (new_ids >= first_new) & np.isin(cand, uniq[cnt == 1])
         prev_uv = _keypoints(prev["feats"])[ref_indices[no_id][is_new]] if prev is not None else None
-        win.add(self.T_wc, _keypoints(curr_feats), curr_ids, prev_uv, new_ids[is_new])
+        prev_ids = new_ids[is_new]
+        if found is not None and len(found[1]):  # the epipolar search's landmarks: their other ray too
+            prev_uv = np.concatenate([np.asarray(prev_uv, np.float32).reshape(-1, 2), found[0]])
+            prev_ids = np.concatenate([prev_ids, found[1]])
+        win.add(self.T_wc, _keypoints(curr_feats), curr_ids, prev_uv, prev_ids)
         if getattr(cfg, "ba_enabled", False):
             self._vo_amd_last_ba = run_window_ba(self, win)
 
@@ -331,6 +341,78 @@ def reobserve_map(vo, curr_feats, curr_ids, first_new: int) -> int:
                                 unique=True, image_size=size)
     curr_ids[free[pairs[:, 1]]] = ids[pairs[:, 0]]
     return len(pairs)
+
+
+def epipolar_search(vo, prev, curr_feats, curr_ids, ref_indices, curr_indices):
+    """``cfg.map_epipolar_search``: new landmarks from the keypoints the ratio-test match dropped.
+
+    Queries are the previous keyframe's keypoints that have no id and took no part in the match
+    (not in ``ref_indices``); train rows are the new frame's keypoints without an id that took no
+    part either (not in ``curr_indices``), so the landmarks the keyframe's own association made or
+    carried keep their keypoints, and the ids made here never sit on a matched keypoint.  Both
+    poses are known, so each query is looked for only along its epipolar segment in the new frame
+    (:func:`visualodometry_amd.matcher.epipolar_segments` over the configured depth range, then
+    :func:`visualodometry_amd.matcher.match_segment`, one-to-one).  The pairs are triangulated
+    and filtered as the keyframe's own (``triangulate_points``: ``cfg.min_depth``,
+    ``cfg.max_reproj_err``); each kept point takes ``next_pt_id`` in ascending query order, goes
+    into ``map_points`` as float32 and into ``curr_ids``, and with ``cfg.map_reobserve`` its
+    descriptor into the landmark descriptor store.  ``_prune_map`` runs once more.
+
+    Returns ``(uv (M, 2) float32, ids (M,) int64)``: the new landmarks' observations in the
+    previous keyframe, for the window."""
+    from .. import matcher, triangulate
+
+    cfg = vo.cfg
+    none = np.zeros((0, 2), np.float32), np.zeros(0, np.int64)
+    prev_ids = np.asarray(prev["ids"])
+    q_mask = prev_ids == -1
+    q_mask[np.asarray(ref_indices, np.int64)] = False
+    t_mask = curr_ids == -1
+    t_mask[np.asarray(curr_indices, np.int64)] = False
+    q, free = np.flatnonzero(q_mask), np.flatnonzero(t_mask)
+    if q.size == 0 or free.size == 0:
+        return none
+    kp0, kp1 = _keypoints(prev["feats"]), _keypoints(curr_feats)
+    size = _image_size(curr_feats, vo.K)
+    T_cw_prev, T_cw_cur = np.linalg.inv(prev["T_wc"]), np.linalg.inv(vo.T_wc)
+    z_max = float(getattr(cfg, "map_epipolar_max_depth", 0.0))
+    seg, valid = matcher.epipolar_segments(kp0[q], T_cw_prev, T_cw_cur, vo.K, size,
+                                           float(getattr(cfg, "map_epipolar_min_depth", 1.0)),
+                                           z_max if z_max > 0 else np.inf,
+                                           float(getattr(cfg, "map_epipolar_min_length", 8.0)))
+    if not valid.any():
+        return none
+    q, seg = q[valid], seg[valid]  # (a keypoint without a segment would only be an inactive query)
+    max_dist = getattr(cfg, "map_epipolar_max_dist", None)
+    if max_dist is None:
+        max_dist = 0.7 if getattr(cfg, "extractor_type", "sift") == "superpoint" else 300.0
+    des0, des1 = _descriptors(prev["feats"]), _descriptors(curr_feats)
+    kp = curr_feats["keypoints"]
+    kp = kp[0] if getattr(kp, "ndim", 2) == 3 else kp
+    pairs = matcher.match_segment(_np(_rows(des0, q)), seg, float(getattr(cfg, "map_epipolar_radius", 2.0)),
+                                  _rows(des1, free), _rows(kp, free),
+                                  ratio=float(getattr(cfg, "map_epipolar_ratio", 0.8)), max_dist=float(max_dist),
+                                  unique=True, image_size=size)
+    if len(pairs) == 0:
+        return none
+    qi, ci = q[pairs[:, 0]], free[pairs[:, 1]]
+    pts3d, keep = triangulate.triangulate_points(T_cw_prev, T_cw_cur, kp0[qi], kp1[ci], vo.K, cfg)
+    keep = np.asarray(keep, bool)
+    if not keep.any():
+        return none
+    qi, ci = qi[keep], ci[keep]
+    ids = np.arange(vo.next_pt_id, vo.next_pt_id + len(qi), dtype=np.int64)
+    for pid, X in zip(ids, np.asarray(pts3d, np.float32).reshape(-1, 3)):
+        vo.map_points[int(pid)] = X
+    curr_ids[ci] = ids
+    vo.next_pt_id += len(ids)
+    store = getattr(vo, "_vo_amd_lm_desc", None)
+    if getattr(cfg, "map_reobserve", False) and store is not None:
+        store.put(ids, _np(_rows(des1, ci)))
+    prune = getattr(vo, "_prune_map", None)
+    if prune is not None:
+        prune()
+    return np.asarray(kp0[qi], np.float32).reshape(-1, 2), ids
 
 
 def run_window_ba(vo, win: KeyframeWindow):

@@ -160,14 +160,14 @@ def _gpu_tensors(des0, des1, ctx):
     return _tensor_2d(des0), _tensor_2d(des1)
 
 
-def _as_xy(p, what: str) -> np.ndarray:
+def _as_xy(p, what: str, cols: int = 2) -> np.ndarray:
     if hasattr(p, "detach"):
         p = p.detach().cpu().numpy()
     p = np.asarray(p)
     if p.ndim == 3 and p.shape[0] == 1:  # (1, N, 2) feature-dict layout
         p = p[0]
-    if p.ndim != 2 or p.shape[1] != 2:
-        raise ValueError(f"{what} must be (N, 2), got shape {p.shape}")
+    if p.ndim != 2 or p.shape[1] != cols:
+        raise ValueError(f"{what} must be (N, {cols}), got shape {p.shape}")
     return np.ascontiguousarray(p, dtype=np.float32)
 
 
@@ -189,12 +189,37 @@ def match_gated(des0, pred, radius, des1, kp1, ratio: float = RATIO_THRESH, max_
 
     Returns ``(M, 2)`` int64 (query, train) pairs in ascending query order, and with
     ``return_dist`` also their float32 distances."""
+    return _match_gate("circle", des0, pred, radius, des1, kp1, ratio, max_dist, unique, image_size, return_dist, ctx)
+
+
+def match_segment(des0, seg, radius, des1, kp1, ratio: float = RATIO_THRESH, max_dist: float = 0.0,
+                  unique: bool = True, image_size=None, return_dist: bool = False,
+                  ctx: _lib.Context | None = None):
+    """Segment-gated matching (``vo_match_segment``): :func:`match_gated` with a capsule for a gate.
+    Query row ``i`` is compared only with the train rows whose keypoint ``kp1[j]`` lies within
+    ``radius[i]`` pixels of the segment ``seg[i] = (ax, ay, bx, by)`` given in the train image; see
+    ``include/vo_hip.h`` for the exact gate.  A zero-length segment is :func:`match_gated`'s circle to
+    the bit; :func:`epipolar_segments` makes the segments of the epipolar search for new landmarks.
+
+    ``seg`` is ``(n0, 4)`` host data (a non-finite value makes the query inactive, as a negative or
+    NaN radius does); every other argument, the tensors read in place, the fallback, the return
+    types, the empty-input behaviour and the errors are :func:`match_gated`'s."""
+    return _match_gate("segment", des0, seg, radius, des1, kp1, ratio, max_dist, unique, image_size, return_dist, ctx)
+
+
+# gate -> (C entry, its options struct, the per-query array's field, its columns)
+_GATES = {"circle": ("vo_match_gated", _lib.MatchGateOptionsC, "pred", 2),
+          "segment": ("vo_match_segment", _lib.MatchSegmentOptionsC, "seg", 4)}
+
+
+def _match_gate(gate, des0, query, radius, des1, kp1, ratio, max_dist, unique, image_size, return_dist, ctx):
     ctx = ctx or _lib.context()
     a = _as_des(des0)
-    p = _as_xy(pred, "pred")
+    fn, options, what, cols = _GATES[gate]
+    p = _as_xy(query, what, cols)
     n0, dim = a.shape
     if p.shape[0] != n0:
-        raise ValueError(f"pred has {p.shape[0]} rows for {n0} query rows")
+        raise ValueError(f"{what} has {p.shape[0]} rows for {n0} query rows")
     rad = None
     radius0 = 0.0
     if np.ndim(radius) == 0:
@@ -226,21 +251,21 @@ def match_gated(des0, pred, radius, des1, kp1, ratio: float = RATIO_THRESH, max_
         flags |= _lib.VO_MATCH_DEVICE_PTRS
     else:
         p1, pk = b.ctypes.data, k.ctypes.data
-    opt = _lib.MatchGateOptionsC(pred=p.ctypes.data, radius=rad.ctypes.data if rad is not None else None, kp1=pk,
-                                 radius0=radius0, width=width, height=height, ratio=float(ratio),
-                                 max_dist=float(max_dist), flags=flags, reserved=0)
+    opt = options(radius=rad.ctypes.data if rad is not None else None, kp1=pk, radius0=radius0, width=width,
+                  height=height, ratio=float(ratio), max_dist=float(max_dist), flags=flags, reserved=0,
+                  **{what: p.ctypes.data})
     out = np.empty((n0, 2), dtype=np.int32)
     dist = np.empty(n0, dtype=np.float32)
     cnt = np.zeros(1, dtype=np.int32)
-    rc = ctx.lib.vo_match_gated(ctx.handle, C.c_void_p(a.ctypes.data), n0, C.c_void_p(p1), n1, dim, C.byref(opt),
-                                ptr(out, C.c_int32), ptr(dist, C.c_float), ptr(cnt, C.c_int32))
+    rc = getattr(ctx.lib, fn)(ctx.handle, C.c_void_p(a.ctypes.data), n0, C.c_void_p(p1), n1, dim, C.byref(opt),
+                              ptr(out, C.c_int32), ptr(dist, C.c_float), ptr(cnt, C.c_int32))
     if dev is not None and rc == _lib.VO_ERR_ARG:
         # torch's device memory is not this library's HIP runtime's (the library refuses such
         # pointers before any launch): the host path from here on
         ctx._foreign_tensors = True
-        return match_gated(a, p, rad if rad is not None else radius0, des1.detach().cpu(), kp1.detach().cpu(), ratio,
-                           max_dist, unique, image_size, return_dist, ctx)
-    check(rc, "vo_match_gated")
+        return _match_gate(gate, a, p, rad if rad is not None else radius0, des1.detach().cpu(), kp1.detach().cpu(),
+                           ratio, max_dist, unique, image_size, return_dist, ctx)
+    check(rc, fn)
     m = int(cnt[0])
     pairs = out[:m].astype(np.int64)
     return (pairs, dist[:m].copy()) if return_dist else pairs
@@ -268,6 +293,68 @@ def project_points(points_w, T_cw, K, image_size, min_depth: float = 0.0):
     with np.errstate(over="ignore", invalid="ignore"):
         pred = np.stack([u, v], axis=1).astype(np.float32)
     return pred, valid
+
+
+EPIPOLAR_NEAR = 1e-3  # depth in the second camera at which a ray crossing its camera plane is cut
+
+
+def epipolar_segments(kp0, T_cw0, T_cw1, K, image_size, z_min: float, z_max: float = np.inf,
+                      min_length: float = 0.0):
+    """Where keypoints of view 0 can reappear in view 1: ``(seg float32 (n, 4), valid bool (n,))``,
+    ``seg[i] = (ax, ay, bx, by)`` for :func:`match_segment`.
+
+    ``kp0[i]`` is back-projected to the depths ``z_min`` and ``z_max`` in camera 0 (``inf``: the
+    point at infinity of its ray, whose image is the vanishing point), both are taken into camera 1
+    (``T_cw`` (4, 4) world -> camera), the 3-D segment is cut at depth ``EPIPOLAR_NEAR`` where it
+    crosses camera 1's plane, its ends are projected with ``K`` and the image segment is clipped to
+    ``[0, width] x [0, height]``.  ``a`` is the near end.  ``valid`` is false when nothing is left
+    (the whole range lies behind camera 1 or projects outside the image), when the result is not
+    finite, or when the clipped segment is shorter than ``min_length`` pixels: the depth of such a
+    keypoint is not observable from this pair.  An invalid row is NaN: an inactive query of
+    :func:`match_segment`.
+    Computed in numpy float64 and cast once."""
+    kp = np.asarray(kp0, np.float64).reshape(-1, 2)
+    K = np.asarray(K, np.float64)
+    T10 = np.asarray(T_cw1, np.float64) @ np.linalg.inv(np.asarray(T_cw0, np.float64))
+    R, t = T10[:3, :3], T10[:3, 3]
+    n = len(kp)
+    width, height = float(image_size[0]), float(image_size[1])
+    z_min, z_max = float(z_min), float(z_max)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d0 = np.stack([(kp[:, 0] - K[0, 2]) / K[0, 0], (kp[:, 1] - K[1, 2]) / K[1, 1], np.ones(n)], axis=1)
+        d = d0 @ R.T  # the ray in camera 1: X(z) = z d + t, z the depth in camera 0
+        c = d[:, 2]
+        # the depths z at which the point is at least EPIPOLAR_NEAR in front of camera 1
+        cut = (EPIPOLAR_NEAR - t[2]) / c
+        lo = np.where(c > 0, np.maximum(z_min, cut), z_min)
+        hi = np.where(c < 0, np.minimum(z_max, cut), z_max)
+        ok = (lo <= hi) & ((c != 0) | (t[2] >= EPIPOLAR_NEAR))
+
+        def project(z):
+            far = np.isinf(z)  # the vanishing point: the projection of the direction
+            zz = np.where(far, 0.0, z)
+            X = np.where(far[:, None], d, zz[:, None] * d + t)
+            return np.stack([K[0, 0] * X[:, 0] / X[:, 2] + K[0, 2], K[1, 1] * X[:, 1] / X[:, 2] + K[1, 2]], axis=1)
+
+        a, b = project(lo), project(hi)
+        ok &= np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1)
+        # Liang-Barsky: the part a + s (b - a), s in [s0, s1], inside the rectangle
+        e = b - a
+        s0, s1 = np.zeros(n), np.ones(n)
+        for p, q in ((-e[:, 0], a[:, 0]), (e[:, 0], width - a[:, 0]), (-e[:, 1], a[:, 1]), (e[:, 1], height - a[:, 1])):
+            ok &= (p != 0) | (q >= 0)  # parallel to this border and outside it
+            r = q / p
+            s0 = np.where(p < 0, np.maximum(s0, r), s0)
+            s1 = np.where(p > 0, np.minimum(s1, r), s1)
+        ok &= s0 <= s1
+        ca, cb = a + s0[:, None] * e, a + s1[:, None] * e
+        hi_xy = np.array([width, height])
+        ca, cb = np.clip(ca, 0.0, hi_xy), np.clip(cb, 0.0, hi_xy)  # (rounding only: the ends are on the border)
+        seg = np.concatenate([ca, cb], axis=1)
+        ok &= np.isfinite(seg).all(axis=1)
+        ok &= np.hypot(cb[:, 0] - ca[:, 0], cb[:, 1] - ca[:, 1]) >= float(min_length)
+        seg = np.where(ok[:, None], seg, np.nan).astype(np.float32)
+    return seg, ok
 
 
 def match_knn2(des0, des1, ctx: _lib.Context | None = None):
