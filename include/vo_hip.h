@@ -789,6 +789,64 @@ int vo_sift_detect_and_compute_batch_async(vo_ctx* ctx, const uint8_t* d_imgs, i
  * [h, w, pitch, G offset, DoG offset]; returns the count of values (writes up to n). */
 int vo_sift_layout(int h, int w, int n_layers, int64_t* out, int n);
 
+/* ---- KLT tracking (sparse pyramidal Lucas-Kanade) ------------------------ */
+/* Tracks n points from img0 into img1 (h x w uint8, row-major): the structure of OpenCV's
+ * calcOpticalFlowPyrLK (fixed-point patches, a double 2 x 2 solve), not its bits.  Build-defined:
+ * the reference has no tracker.  The contract is DESIGN.md §KLT, restated in tests/klt_ref.py;
+ * every sum over a window is an integer, so results do not depend on how the device computes them.
+ *   Pyramid: level l + 1 is ((w_l + 1) / 2) x ((h_l + 1) / 2), each pixel
+ *   (sum_{i,j=-2..2} k_i k_j I_l(2x+i, 2y+j) + 128) >> 8 with k = 1 4 6 4 1 and indices reflected
+ *   without repeating the edge.  L_eff is the largest L <= opt->levels whose level L - 1 is at
+ *   least (2r+3) x (2r+3), at least 1; a level 0 smaller than that gives every point status 1.
+ *   Window: (2r+1)^2 pixels with corner q = c - r (float32), iq = floor(q), inside iff
+ *   0 <= iq.x <= w_l - 2r - 2 and 0 <= iq.y <= h_l - 2r - 2 (a non-finite q is outside); bilinear
+ *   weights x 16384 from the fractions, intensities x 32, Scharr derivatives, all integers.
+ *   Per level from L_eff - 1 down to 0: the template at p0 * 2^-l, A = sum of derivative
+ *   products (int64) scaled by 2^-20, minEig and D in double; a start window outside, or
+ *   minEig < min_eig or D < FLT_EPSILON, skips the level (status 1 / 2 at level 0).  Then at most
+ *   max_iters steps n += (float)delta from the integer mismatch sums, stopped by
+ *   |delta|^2 <= eps^2 or OpenCV's oscillation rule; a window at n outside ends the level
+ *   (status 3 at level 0, also for the final n).  err = (float)(sum |J - I| / (32 (2r+1)^2)) at
+ *   the final n.
+ *   Options: max_err > 0 gives status 5 to err > max_err.  VO_KLT_GUESS: pts1 holds the start of
+ *   n on entry.  VO_KLT_FB: every accepted point is tracked back from img1 to img0 with p0 as the
+ *   guess under the same options; a back track that fails, or ends with
+ *   (double)dx*dx + (double)dy*dy > (double)fb_thresh*fb_thresh from p0, gives status 4.
+ *   Status: 0 tracked, 1 start window outside, 2 degenerate texture, 3 left the image,
+ *   4 forward-backward check failed, 5 err above max_err, 6 non-finite p0 or guess.  pts1 of a
+ *   failed point is p0 and its err 0.  *n_tracked (optional, as err) counts status 0.
+ * All arrays are host arrays: pts0, pts1 (n, 2) float32 pixels (x, y), status (n), err (n).  A
+ * nonzero tag keys the context's device pyramid cache (at least 4 entries, keyed by
+ * (tag, h, w, levels built), least recently used evicted): on a hit the image is neither uploaded
+ * nor rebuilt and may be NULL; the caller changes the tag when the pixels change, as with
+ * des0_tag.  Results never depend on the cache.
+ *   VO_ERR_ARG (before the context or a device is touched): opt, pts1 or status NULL, pts0 NULL
+ *   with n > 0, negative n, h < 1 or w < 1, a NULL image with tag 0, win_radius outside 1..15,
+ *   levels outside 1..8, max_iters outside 1..100, a non-finite or negative eps, min_eig,
+ *   fb_thresh or max_err, unknown flag bits, reserved != 0.  n == 0: VO_OK, *n_tracked = 0.
+ * The kernels are not in the profiler's id table (tools/klt_timing.py times the call). */
+#define VO_KLT_GUESS 1   /* pts1 holds the initial guess on entry */
+#define VO_KLT_FB    2   /* forward-backward check */
+typedef struct {
+  int32_t win_radius;  /* 1..15 */
+  int32_t levels;      /* 1..8 */
+  int32_t max_iters;   /* 1..100 */
+  float eps, min_eig, fb_thresh, max_err;
+  int32_t flags;       /* VO_KLT_GUESS | VO_KLT_FB */
+  int32_t reserved;    /* 0 */
+} vo_klt_options;
+int vo_klt_track(vo_ctx* ctx, const uint8_t* img0, uint64_t tag0, const uint8_t* img1, uint64_t tag1, int h, int w,
+                 const float* pts0, float* pts1, int n, const vo_klt_options* opt, uint8_t* status, float* err,
+                 int32_t* n_tracked);
+/* Parity/debug: the pyramid of one image, levels concatenated and unpitched (cap = capacity of
+ * out in bytes).  Levels are built while they are at least 3 x 3 (vo_klt_layout with
+ * win_radius 0); *levels_out = how many. */
+int vo_klt_pyramid(vo_ctx* ctx, const uint8_t* img, int h, int w, int levels, uint8_t* out, int64_t cap,
+                   int32_t* levels_out);
+/* Host only: [L_eff, bytes of the pyramid] then per level [h, w, byte offset]; returns the count
+ * of values (writes up to n), or VO_ERR_ARG. */
+int vo_klt_layout(int h, int w, int levels, int win_radius, int64_t* out, int n);
+
 /* ---- multi-GPU (landmark sharding + RCCL all-reduce) --------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller. */
 int vo_comm_unique_id(char out[128]);

@@ -90,6 +90,17 @@ class MatchSegmentOptionsC(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+VO_KLT_GUESS = 1  # vo_klt_track flags: pts1 holds the initial guess on entry
+VO_KLT_FB = 2     # forward-backward check
+
+
+class KltOptionsC(C.Structure):
+    """``vo_klt_options``: window, pyramid, iteration and acceptance settings of ``vo_klt_track``."""
+    _fields_ = [("win_radius", C.c_int32), ("levels", C.c_int32), ("max_iters", C.c_int32), ("eps", C.c_float),
+                ("min_eig", C.c_float), ("fb_thresh", C.c_float), ("max_err", C.c_float), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class BAProblemC(C.Structure):
     _fields_ = [
         ("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_obs", C.c_int32),
@@ -172,6 +183,10 @@ SIGNATURES = {
     "vo_pnp_subsets": (_I, [_I, _I, _PI32]),
     "vo_essential_ransac": (_I, [_P, _PF, _PF, _I, _PD, _I, _D, _D, _PD, C.POINTER(C.c_uint8), _PI32, _PI32]),
     "vo_recover_pose": (_I, [_P, _PD, _PF, _PF, _I, _PD, _D, _PD, _PD, C.POINTER(C.c_uint8), _PI32]),
+    "vo_klt_track": (_I, [_P, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _I, _I, C.c_void_p, C.c_void_p, _I,
+                          C.POINTER(KltOptionsC), C.c_void_p, C.c_void_p, _PI32]),
+    "vo_klt_pyramid": (_I, [_P, C.c_void_p, _I, _I, _I, C.c_void_p, C.c_int64, _PI32]),
+    "vo_klt_layout": (_I, [_I, _I, _I, _I, _PI64, _I]),
     "vo_sift_detect": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _D, _D, _D, _I, _I, _PF, _PI32, _PI32]),
     "vo_sift_detect_batch_async": (_I, [_P, _P, _I, _I, _I, _D, _D, _D, _I, _I, _P, _P, _P]),
     "vo_sift_pyramid": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _D, _I, _PF, C.c_int64, _PF, C.c_int64]),

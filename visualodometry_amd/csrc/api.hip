@@ -438,6 +438,56 @@ int vo_recover_pose(vo_ctx* ctx, const double* E, const float* pts1, const float
   });
 }
 
+int vo_klt_track(vo_ctx* ctx, const uint8_t* img0, uint64_t tag0, const uint8_t* img1, uint64_t tag1, int h, int w,
+                 const float* pts0, float* pts1, int n, const vo_klt_options* opt, uint8_t* status, float* err,
+                 int32_t* n_tracked) {
+  return guarded([&] {
+    // the arguments' own checks first: they need no device (nor a context)
+    VO_REQUIRE(opt && pts1 && status, VO_ERR_ARG, "vo_klt_track: null options or outputs");
+    VO_REQUIRE(n >= 0 && h >= 1 && w >= 1, VO_ERR_ARG, "vo_klt_track: bad shape n=%d h=%d w=%d", n, h, w);
+    VO_REQUIRE(n == 0 || pts0, VO_ERR_ARG, "vo_klt_track: null pts0 with n > 0");
+    VO_REQUIRE((img0 || tag0) && (img1 || tag1), VO_ERR_ARG, "vo_klt_track: null image with tag 0");
+    VO_REQUIRE(opt->win_radius >= 1 && opt->win_radius <= 15, VO_ERR_ARG, "vo_klt_track: win_radius %d outside 1..15",
+               opt->win_radius);
+    VO_REQUIRE(opt->levels >= 1 && opt->levels <= 8, VO_ERR_ARG, "vo_klt_track: levels %d outside 1..8", opt->levels);
+    VO_REQUIRE(opt->max_iters >= 1 && opt->max_iters <= 100, VO_ERR_ARG, "vo_klt_track: max_iters %d outside 1..100",
+               opt->max_iters);
+    auto good = [](float v) { return std::isfinite(v) && v >= 0.f; };
+    VO_REQUIRE(good(opt->eps), VO_ERR_ARG, "vo_klt_track: eps must be finite and >= 0");
+    VO_REQUIRE(good(opt->min_eig), VO_ERR_ARG, "vo_klt_track: min_eig must be finite and >= 0");
+    VO_REQUIRE(good(opt->fb_thresh), VO_ERR_ARG, "vo_klt_track: fb_thresh must be finite and >= 0");
+    VO_REQUIRE(good(opt->max_err), VO_ERR_ARG, "vo_klt_track: max_err must be finite and >= 0");
+    VO_REQUIRE((opt->flags & ~(VO_KLT_GUESS | VO_KLT_FB)) == 0, VO_ERR_ARG, "vo_klt_track: unknown flags 0x%x",
+               opt->flags);
+    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "vo_klt_track: reserved must be 0");
+    if (n_tracked) *n_tracked = 0;
+    if (n == 0) return;
+    vo::bind(ctx);
+    vo::klt_track_host(ctx, img0, tag0, img1, tag1, h, w, pts0, pts1, n, opt, status, err, n_tracked);
+  });
+}
+
+int vo_klt_pyramid(vo_ctx* ctx, const uint8_t* img, int h, int w, int levels, uint8_t* out, int64_t cap,
+                   int32_t* levels_out) {
+  return guarded([&] {
+    VO_REQUIRE(img && out && h >= 1 && w >= 1 && levels >= 1 && levels <= 8, VO_ERR_ARG,
+               "vo_klt_pyramid: bad arguments");
+    vo::bind(ctx);
+    vo::klt_pyramid_host(ctx, img, h, w, levels, out, cap, levels_out);
+  });
+}
+
+int vo_klt_layout(int h, int w, int levels, int win_radius, int64_t* out, int n) {
+  int count = 0;
+  const int rc = guarded([&] {
+    VO_REQUIRE(h >= 1 && w >= 1 && levels >= 1 && levels <= 8 && win_radius >= 0 && win_radius <= 15 && n >= 0 &&
+                   (n == 0 || out),
+               VO_ERR_ARG, "vo_klt_layout: bad arguments");
+    count = vo::klt_layout(h, w, levels, win_radius, out, n);
+  });
+  return rc == VO_OK ? count : rc;
+}
+
 int vo_sift_detect(vo_ctx* ctx, const uint8_t* img, int h, int w, double contrast, double edge, double sigma,
                    int n_layers, int capacity, float* kp_f, int32_t* kp_i, int32_t* count) {
   return guarded([&] {

@@ -103,6 +103,22 @@ struct SiftWorkspace {
   }
 };
 
+// KLT tracker workspace (klt.hip): device pyramids (uint8 levels, concatenated and unpitched).
+struct KltPyramid {
+  DevBuf buf;
+  uint64_t tag = 0;
+  int h = -1, w = -1, levels = -1;  // levels: how many were built (L_eff)
+  uint64_t used = 0;                // the workspace clock at the last use (LRU)
+  bool valid = false;
+};
+constexpr int kKltCacheEntries = 4;
+struct KltWorkspace {
+  KltPyramid cache[kKltCacheEntries];  // pyramids of tagged images, keyed by (tag, h, w, levels)
+  KltPyramid scratch[2];               // pyramids of this call's untagged images
+  DevBuf pts;                          // host-call staging: pts0, pts1, err, status
+  uint64_t clock = 0;
+};
+
 class BAEngine;   // ba_engine.hip
 struct Comm;      // ba_comm.h (RCCL communicator or loopback group)
 
@@ -139,6 +155,7 @@ struct vo_ctx {
   vo::PnpWorkspace pnp;
   vo::EssWorkspace ess;
   vo::SiftWorkspace sift;
+  vo::KltWorkspace klt;
   vo::Profiler prof;
   std::unique_ptr<vo::BAEngine> ba;
   std::unique_ptr<vo::Comm> comm;
@@ -196,6 +213,13 @@ void essential_ransac_host(vo_ctx* ctx, const float* pts1, const float* pts2, in
                            int32_t* inliers_out);
 void recover_pose_host(vo_ctx* ctx, const double* E, const float* pts1, const float* pts2, int n, const double* K,
                        double distance_thresh, double* R_out, double* t_out, uint8_t* mask_out, int32_t* good_out);
+// KLT tracker (klt.hip): host arrays, synchronous; the arguments are checked by the caller.
+void klt_track_host(vo_ctx* ctx, const uint8_t* img0, uint64_t tag0, const uint8_t* img1, uint64_t tag1, int h, int w,
+                    const float* pts0, float* pts1, int n, const vo_klt_options* opt, uint8_t* status, float* err,
+                    int32_t* n_tracked);
+void klt_pyramid_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int levels, uint8_t* out, int64_t cap,
+                      int32_t* levels_out);
+int klt_layout(int h, int w, int levels, int win_radius, int64_t* out, int n);
 // SIFT detection (sift.hip): device images, device keypoint outputs (unsorted).
 void sift_run(vo_ctx* ctx, const uint8_t* d_img, int batch, int h, int w, double contrast, double edge,
               double sigma, int n_layers, int capacity, float* d_kpf, int32_t* d_kpi, int32_t* d_count,

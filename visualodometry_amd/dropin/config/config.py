@@ -98,6 +98,16 @@ class VOConfig:
     map_epipolar_max_depth: float = 0.0  # ... 0 = up to infinity (the segment ends at the vanishing point)
     # a keypoint whose clipped segment is shorter has no observable depth from this pair: not searched
     map_epipolar_min_length: float = 8.0
+    # KLT tracking front end (SIFT extractor only): between two keyframes the keyframe's keypoints are tracked
+    # into every frame (visualodometry_amd.klt.track) instead of detecting and matching; the keyframe's
+    # descriptors ride along, and a new keyframe is replenished by detection away from the tracked points.
+    # All values below are untuned starting values; no accuracy claimed.
+    klt_tracking: bool = False
+    klt_win_radius: int = 10  # window (2r+1)^2, 21 x 21 as cv2.calcOpticalFlowPyrLK's default
+    klt_levels: int = 4  # pyramid levels
+    klt_fb_thresh: float = 1.0  # forward-backward check in pixels
+    klt_min_tracks: int = 50  # fewer survivors: this frame detects and matches as without the route
+    klt_min_distance: float = 8.0  # a replenishing detection keeps this distance from every tracked keypoint
 
 
 # dataset -> (overrides always applied, overrides applied when extractor is SIFT)
@@ -130,8 +140,9 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
     environment switches reach the back end without touching it:
     ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``), ``VO_AMD_BA=1``
     (``ba_enabled``), ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``), ``VO_AMD_INIT=1``
-    (``init_on_gpu``), ``VO_AMD_REOBSERVE=1`` (``map_reobserve``) and ``VO_AMD_EPIPOLAR=1``
-    (``map_epipolar_search``).  Unset, the result equals the reference's.
+    (``init_on_gpu``), ``VO_AMD_REOBSERVE=1`` (``map_reobserve``), ``VO_AMD_EPIPOLAR=1``
+    (``map_epipolar_search``) and ``VO_AMD_KLT=1`` (``klt_tracking``).  Unset, the result equals
+    the reference's.
     """
     cfg = VOConfig()
     if extractor_type is None:
@@ -146,6 +157,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
         cfg.map_reobserve = True
     if os.environ.get("VO_AMD_EPIPOLAR", "0") not in ("", "0"):
         cfg.map_epipolar_search = True
+    if os.environ.get("VO_AMD_KLT", "0") not in ("", "0"):
+        cfg.klt_tracking = True
     if extractor_type is not None:
         cfg.extractor_type = extractor_type
     base, sift = _DATASET_OVERRIDES.get(dataset, ({}, {}))

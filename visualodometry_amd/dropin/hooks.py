@@ -28,6 +28,12 @@ are the caller's environment):
   ``cfg.map_epipolar_search`` (off by default) the keypoints that match left without a partner are
   then looked for along their epipolar segments (:func:`epipolar_search`,
   :func:`visualodometry_amd.matcher.match_segment`) and the pairs triangulated into new landmarks.
+* With ``cfg.klt_tracking`` (off by default, SIFT extractor only) ``process_image`` tracks the
+  keyframe's keypoints into the frame (:func:`klt_process_image`,
+  :func:`visualodometry_amd.klt.track`) instead of detecting, ``match_frames`` returns the pairs a
+  tracked frame brings (:func:`klt_pairs`), and a new keyframe is replenished by detection away
+  from its tracked keypoints (:func:`klt_replenish`).  The settings are read once, when the
+  frontend is constructed; a frontend without the route reads no ``klt_*`` setting on the frame path.
 
 The reference keeps only the current keyframe's observation of a freshly
 triangulated point (``vo.py:277-284``); the window also records the previous
@@ -37,6 +43,8 @@ what makes a two-keyframe landmark constrain BA at all.
 
 from __future__ import annotations
 
+import itertools
+import weakref
 from collections import deque
 from dataclasses import dataclass, field
 
@@ -269,6 +277,10 @@ def _wrap_create_keyframe(orig):
         win.add(self.T_wc, _keypoints(curr_feats), curr_ids, prev_uv, prev_ids)
         if getattr(cfg, "ba_enabled", False):
             self._vo_amd_last_ba = run_window_ba(self, win)
+        fe = getattr(self, "frontend", None)
+        st = getattr(fe, "_vo_amd_klt", None)  # (off: not set; no klt_* setting is read, no call made)
+        if st is not None:
+            klt_replenish(self, st, lambda image: _detect_as_today(fe, image))
 
     _create_keyframe._vo_amd_wrapped = orig
     return _create_keyframe
@@ -415,6 +427,182 @@ def epipolar_search(vo, prev, curr_feats, curr_ids, ref_indices, curr_indices):
     return np.asarray(kp0[qi], np.float32).reshape(-1, 2), ids
 
 
+# ---- cfg.klt_tracking: the KLT tracking front end --------------------------------------------
+# Private keys of a feature dict under the route: the frame's grey image and the tag its device
+# pyramid is cached under, and, on a dict tracked from a keyframe, that keyframe's dict and the
+# keyframe row of each of its rows.
+_KLT_IMAGE, _KLT_TAG, _KLT_SRC, _KLT_SRC_IDX = "_vo_amd_klt_image", "_vo_amd_klt_tag", "_vo_amd_klt_src", \
+    "_vo_amd_klt_src_idx"
+_klt_tags = itertools.count(1 << 40)  # pyramid-cache tags of the frames seen (one per image, never reused)
+
+
+class KltTracker:
+    """State of the ``cfg.klt_tracking`` route on a ``FeatureFrontend``: the settings (read once,
+    at construction), the ``VisualOdometry`` that owns the frontend, and per keyframe dict the
+    keyframe rows still alive with their positions in the previous frame.  A point once lost
+    stays lost until the next keyframe."""
+
+    def __init__(self, config):
+        self.win_radius = int(getattr(config, "klt_win_radius", 10))
+        self.levels = int(getattr(config, "klt_levels", 4))
+        self.fb_thresh = float(getattr(config, "klt_fb_thresh", 1.0))
+        self.min_tracks = int(getattr(config, "klt_min_tracks", 50))
+        self.min_distance = float(getattr(config, "klt_min_distance", 8.0))
+        self.max_rows = int(getattr(config, "sift_n_features", 0) or 0)
+        self.owner = None  # weakref to the VisualOdometry (set by its wrapped __init__)
+        self.reset()
+
+    def reset(self) -> None:
+        self.src = None    # the keyframe dict the state below belongs to
+        self.alive = None  # (M,) int64 keyframe rows still tracked
+        self.last = None   # (M, 2) float32 their positions in the previous frame: the next guess
+        self.kp0 = None    # (N, 2) float32 the keyframe's keypoints
+
+    def keyframe(self):
+        vo = self.owner() if self.owner is not None else None
+        return getattr(vo, "keyframe", None) if vo is not None else None
+
+
+def _like(a, ref):
+    """The numpy array ``a`` as ``ref``'s kind: a tensor on ``ref``'s device, or numpy."""
+    if hasattr(ref, "detach"):
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(a)).to(ref.device)
+    return a
+
+
+def _batched(a, ref):
+    return a[None] if getattr(ref, "ndim", 2) == 3 else a
+
+
+def klt_process_image(st: KltTracker, img, detect):
+    """``process_image`` under ``cfg.klt_tracking``.  Without a keyframe that carries its image,
+    ``detect()`` (the frame path without the route) and the image attached; otherwise the
+    keyframe's live keypoints tracked into ``img``: the survivors' positions as ``keypoints``,
+    their keyframe descriptors as ``descriptors``.  Fewer than ``klt_min_tracks`` survivors:
+    ``detect()`` for this frame."""
+    from .. import klt
+
+    if np.ndim(img) != 2 or getattr(img, "dtype", None) != np.uint8:
+        return detect()  # the route tracks grey uint8 frames only
+    tag = next(_klt_tags)
+
+    def detected():
+        feats = detect()
+        if isinstance(feats, dict):
+            feats[_KLT_IMAGE], feats[_KLT_TAG] = img, tag
+        return feats
+
+    kf = st.keyframe()
+    src = kf.get("feats") if isinstance(kf, dict) else None
+    if not isinstance(src, dict) or src.get(_KLT_IMAGE) is None or src[_KLT_IMAGE].shape != img.shape:
+        return detected()
+    kp_ref = src["keypoints"]
+    if st.src is not src:  # a new keyframe: all of its rows are alive again
+        st.src = src
+        st.last = np.ascontiguousarray(_keypoints(src), np.float32).reshape(-1, 2)
+        st.alive = np.arange(len(st.last), dtype=np.int64)
+        st.kp0 = st.last.copy()
+    if st.alive.size < st.min_tracks:
+        return detected()
+    p1, status, _ = klt.track(src[_KLT_IMAGE], img, st.kp0[st.alive], guess=st.last, win_radius=st.win_radius,
+                              levels=st.levels, fb_thresh=st.fb_thresh if st.fb_thresh > 0 else None,
+                              tags=(src[_KLT_TAG], tag))
+    ok = status == 0
+    st.alive, st.last = st.alive[ok], np.ascontiguousarray(p1[ok])
+    if st.alive.size < st.min_tracks:
+        return detected()
+    feats = {
+        "keypoints": _batched(_like(st.last, kp_ref), kp_ref),
+        "descriptors": _batched(_rows(_descriptors(src), st.alive), src["descriptors"]),
+        _KLT_IMAGE: img, _KLT_TAG: tag, _KLT_SRC: src, _KLT_SRC_IDX: st.alive,
+    }
+    if "image_size" in src:
+        feats["image_size"] = src["image_size"]
+    return feats
+
+
+def klt_pairs(feats0: dict, feats1: dict):
+    """The pairs of a dict tracked from ``feats0`` (``None`` when ``feats1`` is anything else)."""
+    if not isinstance(feats1, dict) or feats1.get(_KLT_SRC) is not feats0 or feats0 is None:
+        return None
+    idx = np.asarray(feats1[_KLT_SRC_IDX], np.int64)
+    return np.stack([idx, np.arange(idx.size, dtype=np.int64)], 1)
+
+
+def far_from(kept: np.ndarray, cand: np.ndarray, dist: float) -> np.ndarray:
+    """Which rows of ``cand`` (N, 2) are at least ``dist`` from every row of ``kept`` (M, 2): a grid
+    of ``dist``-sized cells over ``kept``, each candidate tested against its 3 x 3 cells."""
+    cand = np.asarray(cand, np.float64).reshape(-1, 2)
+    kept = np.asarray(kept, np.float64).reshape(-1, 2)
+    ok = np.ones(len(cand), bool)
+    if not len(kept) or not len(cand) or not dist > 0:
+        return ok
+    lo = np.floor(min(kept.min(), cand.min()) / dist) - 1
+    kc = (np.floor(kept / dist) - lo).astype(np.int64)
+    cc = (np.floor(cand / dist) - lo).astype(np.int64)
+    W = int(max(kc[:, 0].max(), cc[:, 0].max())) + 2
+    kkey = kc[:, 1] * W + kc[:, 0]
+    order = np.argsort(kkey, kind="stable")
+    kkey, kept = kkey[order], kept[order]
+    ckey = cc[:, 1] * W + cc[:, 0]
+    for dy in (-1, 0, 1):
+        for dx in (-1, 0, 1):
+            a = np.searchsorted(kkey, ckey + dy * W + dx, "left")
+            b = np.searchsorted(kkey, ckey + dy * W + dx, "right")
+            for j in range(int((b - a).max())):
+                i = a + j
+                live = i < b
+                d = kept[np.minimum(i, len(kept) - 1)] - cand
+                ok &= ~(live & ((d * d).sum(1) < dist * dist))
+    return ok
+
+
+def klt_replenish(vo, st: KltTracker, detect) -> int:
+    """After a keyframe was made from a tracked frame: detect on its image, keep the detections at
+    least ``klt_min_distance`` from every keypoint it has, and append them (evenly thinned to what
+    ``sift_n_features`` rows leave room for) with id -1 to ``keyframe["feats"]`` / ``["ids"]``.
+    The rows the keyframe had keep their indices.  Returns how many rows were appended."""
+    kf = vo.keyframe
+    feats = kf.get("feats") if isinstance(kf, dict) else None
+    if not isinstance(feats, dict) or feats.get(_KLT_SRC) is None or feats.get(_KLT_IMAGE) is None:
+        return 0  # a detected frame is complete already
+    det = detect(feats[_KLT_IMAGE])
+    kept = np.asarray(_keypoints(feats), np.float32).reshape(-1, 2)
+    new = np.flatnonzero(far_from(kept, _keypoints(det), st.min_distance))
+    room = max(st.max_rows - len(kept), 0) if st.max_rows > 0 else new.size
+    if new.size > room:  # evenly over the detector's order, which runs across the image
+        new = new[np.linspace(0, new.size - 1, room).round().astype(np.int64)] if room else new[:0]
+    kp, des = feats["keypoints"], feats["descriptors"]
+    add_kp = _rows(det["keypoints"][0] if getattr(det["keypoints"], "ndim", 2) == 3 else det["keypoints"], new)
+    add_des = _rows(_descriptors(det), new)
+
+    def cat(old, add):
+        rows = old[0] if getattr(old, "ndim", 2) == 3 else old
+        if hasattr(rows, "detach"):
+            import torch
+
+            out = torch.cat([rows, torch.as_tensor(add, dtype=rows.dtype, device=rows.device)])
+        else:
+            out = np.concatenate([rows, np.asarray(_np(add), rows.dtype)])
+        return _batched(out, old)
+
+    full = {k: v for k, v in feats.items() if k not in (_KLT_SRC, _KLT_SRC_IDX)}
+    full["keypoints"], full["descriptors"] = cat(kp, add_kp), cat(des, add_des)
+    ids = np.asarray(kf["ids"])
+    kf["feats"] = full
+    kf["ids"] = np.concatenate([ids, np.full(new.size, -1, ids.dtype)])
+    return int(new.size)
+
+
+def _detect_as_today(frontend, image):
+    """``process_image`` of ``frontend`` without the route: the wrapped method's detection path when
+    the hooks are installed, else the class's own method."""
+    pi = type(frontend).process_image
+    return getattr(pi, "_vo_amd_detect", pi)(frontend, image)
+
+
 def run_window_ba(vo, win: KeyframeWindow):
     """Adjust the window and write poses/points back into the VO state; never raises on bad windows."""
     window, lm_ids = win.build(vo.map_points)
@@ -470,6 +658,9 @@ def _wrap_init(orig):
         _PNP_ON_GPU[0] = bool(getattr(self.cfg, "pnp_on_gpu", True))
         _INIT_ON_GPU[0] = bool(getattr(self.cfg, "init_on_gpu", False))
         _use_map_store(self)
+        st = getattr(getattr(self, "frontend", None), "_vo_amd_klt", None)
+        if st is not None:  # cfg.klt_tracking: the frontend tracks from its owner's keyframe
+            st.owner = weakref.ref(self)
         if getattr(self.cfg, "ba_enabled", False):
             # the BA context pre-sized for a full window (ba_window keyframes, the map's
             # MAX_POINTS cap, vo.py:38) now, so no keyframe call of the drive pays for it
@@ -505,6 +696,9 @@ def _wrap_reset(orig):
         store = getattr(self, "_vo_amd_lm_desc", None)
         if store is not None:
             store.clear()
+        st = getattr(getattr(self, "frontend", None), "_vo_amd_klt", None)
+        if st is not None:
+            st.reset()
 
     _reset_system._vo_amd_wrapped = orig
     return _reset_system
@@ -523,6 +717,10 @@ def _wrap_frontend_init(orig):
             self.extractor = sift.SIFT_create(nfeatures=config.sift_n_features,
                                               contrastThreshold=config.sift_contrast_threshold,
                                               edgeThreshold=config.sift_edge_threshold, sigma=config.sift_sigma)
+        # the KLT tracking front end (SIFT extractor only): its settings are read here, once, so the
+        # frame path of a frontend without the route reads no klt_* setting at all
+        if getattr(config, "extractor_type", None) == "sift" and getattr(config, "klt_tracking", False):
+            self._vo_amd_klt = KltTracker(config)
 
     __init__._vo_amd_wrapped = orig
     return __init__
@@ -532,6 +730,12 @@ def _wrap_process_image(orig):
     from .. import sift
 
     def process_image(self, img):  # FeatureFrontend.process_image, frontend.py:36-75
+        st = self.__dict__.get("_vo_amd_klt")  # cfg.klt_tracking (off: not set, nothing below runs)
+        if st is not None:
+            return klt_process_image(st, img, lambda: detect(self, img))
+        return detect(self, img)
+
+    def detect(self, img):  # the frame path without the route
         ext = getattr(self, "extractor", None)
         dev = getattr(self, "device", None)
         if isinstance(ext, sift.SIFT) and getattr(dev, "type", None) == "cuda" and np.ndim(img) == 2:
@@ -551,6 +755,7 @@ def _wrap_process_image(orig):
         return orig(self, img)
 
     process_image._vo_amd_wrapped = orig
+    process_image._vo_amd_detect = detect
     return process_image
 
 
@@ -558,6 +763,10 @@ def _wrap_match_frames(orig):
     from .. import matcher
 
     def match_frames(self, feats0, feats1):
+        if self.__dict__.get("_vo_amd_klt") is not None:  # cfg.klt_tracking: a tracked frame brings its pairs
+            pairs = klt_pairs(feats0, feats1)
+            if pairs is not None:
+                return pairs
         if getattr(self.conf, "extractor_type", None) == "sift" and getattr(self.conf, "match_on_gpu", True):
             # SIFT integers: the int8 path only, hinted for this call (the context's own hint,
             # which other users of the context may rely on, is restored afterwards)
