@@ -847,6 +847,64 @@ int vo_klt_pyramid(vo_ctx* ctx, const uint8_t* img, int h, int w, int levels, ui
  * of values (writes up to n), or VO_ERR_ARG. */
 int vo_klt_layout(int h, int w, int levels, int win_radius, int64_t* out, int n);
 
+/* ---- Corners (Shi-Tomasi minimum-eigenvalue detector) ------------------- */
+/* Corners of an h x w uint8 image (row-major), strongest first and at least min_distance apart:
+ * the structure of OpenCV's goodFeaturesToTrack, not its bits, plus a set of existing points to
+ * keep away from.  Build-defined; the contract is DESIGN.md §Corners, restated in
+ * tests/corners_ref.py.  Every sum over a block is an integer, so results do not depend on how the
+ * device computes them.
+ *   Image: indices outside are reflected without repeating the edge (-1 -> 1, n -> n - 2, repeated
+ *   as often as needed; an extent of 1 maps everything to 0).
+ *   Gradient (int32, at every pixel through the reflection):
+ *   gx = (I(x+1,y-1) + 2 I(x+1,y) + I(x+1,y+1)) - (I(x-1,y-1) + 2 I(x-1,y) + I(x-1,y+1)), gy alike along y.
+ *   Block sums (int32): a = sum gx^2, b = sum gx gy, c = sum gy^2 over the (2k+1)^2 block centred on
+ *   the pixel, k = block_radius, the gradient field read at reflected indices.
+ *   Response: q = (int64)(a-c)^2 + 4 (int64)b^2; resp = (float)(0.5 * ((double)(a+c) - sqrt((double)q))),
+ *   each operation rounded once, no contraction; defined for every pixel.
+ *   Candidates: rmax = max resp over the pixels whose mask byte is nonzero (all without a mask); no
+ *   corners unless rmax > 0.  A pixel is a candidate iff 1 <= x <= w-2, 1 <= y <= h-2, its mask byte
+ *   is nonzero, (double)resp > (double)quality * (double)rmax, and resp >= the response of each of
+ *   its 8 neighbours (the mask plays no part there; ties keep both).  h < 3 or w < 3: no corners, VO_OK.
+ *   Order: resp descending, ties by y*w + x ascending.
+ *   Selection, d = min_distance, d2 = (double)d*(double)d: walking the candidates in that order, one
+ *   is rejected iff a keep-away point (kx, ky) (float32, both finite; others are ignored) has
+ *   dx*dx + dy*dy < d2 with dx = (double)x - (double)kx (double, one rounding per operation), or an
+ *   already accepted corner has (double)(Dx^2 + Dy^2) < d2 (an integer); else accepted.  The walk
+ *   stops at max_corners accepted.  d = 0 rejects nothing.  Hence the result for max_corners = m
+ *   is the first m rows of the result for any larger limit.
+ *   Output: corners (n, 2) float32 (x, y) (integers), resp (n) (optional), *n_out, in order of acceptance.
+ * All arrays are host arrays.  A nonzero tag looks the image up in the context's KLT pyramid cache
+ * (level 0 of an entry with that tag, h and w): on a hit img may be NULL and nothing is uploaded; on
+ * a miss the image goes into scratch and no entry is created.  Results never depend on the cache.
+ *   VO_ERR_ARG (before the context or a device is touched): opt, corners or n_out NULL, keep NULL
+ *   with n_keep > 0, negative n_keep, h < 1 or w < 1 or h*w > 2^30, a NULL image with tag 0,
+ *   max_corners outside 1..h*w, block_radius outside 1..3, quality not finite or outside (0, 1],
+ *   min_distance not finite or outside 0..1024, nonzero flags or reserved.
+ * The kernels are not in the profiler's id table (tools/corner_timing.py times the call). */
+typedef struct {
+  int32_t max_corners;   /* 1..h*w */
+  int32_t block_radius;  /* 1..3: blocks of 3 x 3, 5 x 5, 7 x 7 */
+  float quality;         /* finite, > 0, <= 1 */
+  float min_distance;    /* finite, 0..1024 */
+  int32_t flags;         /* 0 */
+  int32_t reserved;      /* 0 */
+} vo_corner_options;
+int vo_good_features(vo_ctx* ctx, const uint8_t* img, uint64_t tag, int h, int w, const uint8_t* mask,
+                     const float* keep, int n_keep, const vo_corner_options* opt, float* corners, float* resp,
+                     int32_t* n_out);
+/* Parity/debug: the response map, h*w float32. */
+int vo_corner_response(vo_ctx* ctx, const uint8_t* img, int h, int w, int block_radius, float* out);
+/* The selection rule alone over caller-supplied candidates: xy (n, 2) int32 (each coordinate within
+ * +-2^24), taken in the order resp descending (-0 as +0), ties by row index; out_idx (at least
+ * min(n, max_corners)) receives the accepted rows in order of acceptance.  VO_ERR_ARG also for a
+ * non-finite resp, a negative or non-finite distance (or one above 1024) and max_corners < 1.
+ * n == 0: VO_OK, *n_out = 0, no device touched. */
+int vo_corner_select(vo_ctx* ctx, const int32_t* xy, const float* resp, int n, const float* keep, int n_keep,
+                     float min_distance, int max_corners, int32_t* out_idx, int32_t* n_out);
+/* Debug: the context's last vo_good_features / vo_corner_select call: [candidates, selection
+ * rounds that had something to decide, corners accepted, grid cell side]. */
+int vo_corner_stats(vo_ctx* ctx, int32_t out[4]);
+
 /* ---- multi-GPU (landmark sharding + RCCL all-reduce) --------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller. */
 int vo_comm_unique_id(char out[128]);

@@ -90,6 +90,12 @@ class MatchSegmentOptionsC(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CornerOptionsC(C.Structure):
+    """``vo_corner_options``: limit, block, quality and distance of ``vo_good_features``."""
+    _fields_ = [("max_corners", C.c_int32), ("block_radius", C.c_int32), ("quality", C.c_float),
+                ("min_distance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 VO_KLT_GUESS = 1  # vo_klt_track flags: pts1 holds the initial guess on entry
 VO_KLT_FB = 2     # forward-backward check
 
@@ -187,6 +193,11 @@ SIGNATURES = {
                           C.POINTER(KltOptionsC), C.c_void_p, C.c_void_p, _PI32]),
     "vo_klt_pyramid": (_I, [_P, C.c_void_p, _I, _I, _I, C.c_void_p, C.c_int64, _PI32]),
     "vo_klt_layout": (_I, [_I, _I, _I, _I, _PI64, _I]),
+    "vo_good_features": (_I, [_P, C.c_void_p, C.c_uint64, _I, _I, C.c_void_p, C.c_void_p, _I,
+                              C.POINTER(CornerOptionsC), C.c_void_p, C.c_void_p, _PI32]),
+    "vo_corner_response": (_I, [_P, C.c_void_p, _I, _I, _I, C.c_void_p]),
+    "vo_corner_select": (_I, [_P, C.c_void_p, C.c_void_p, _I, C.c_void_p, _I, C.c_float, _I, C.c_void_p, _PI32]),
+    "vo_corner_stats": (_I, [_P, _PI32]),
     "vo_sift_detect": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _D, _D, _D, _I, _I, _PF, _PI32, _PI32]),
     "vo_sift_detect_batch_async": (_I, [_P, _P, _I, _I, _I, _D, _D, _D, _I, _I, _P, _P, _P]),
     "vo_sift_pyramid": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _D, _I, _PF, C.c_int64, _PF, C.c_int64]),

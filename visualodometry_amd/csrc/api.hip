@@ -488,6 +488,76 @@ int vo_klt_layout(int h, int w, int levels, int win_radius, int64_t* out, int n)
   return rc == VO_OK ? count : rc;
 }
 
+int vo_good_features(vo_ctx* ctx, const uint8_t* img, uint64_t tag, int h, int w, const uint8_t* mask,
+                     const float* keep, int n_keep, const vo_corner_options* opt, float* corners, float* resp,
+                     int32_t* n_out) {
+  return guarded([&] {
+    // the arguments' own checks first: they need no device (nor a context)
+    VO_REQUIRE(opt && corners && n_out, VO_ERR_ARG, "vo_good_features: null options or outputs");
+    VO_REQUIRE(n_keep >= 0 && h >= 1 && w >= 1, VO_ERR_ARG, "vo_good_features: bad shape n_keep=%d h=%d w=%d", n_keep,
+               h, w);
+    VO_REQUIRE((int64_t)h * w <= (int64_t)1 << 30, VO_ERR_ARG, "vo_good_features: bad shape, %d x %d is above 2^30 pixels",
+               h, w);
+    VO_REQUIRE(n_keep == 0 || keep, VO_ERR_ARG, "vo_good_features: null keep with n_keep > 0");
+    VO_REQUIRE(img || tag, VO_ERR_ARG, "vo_good_features: null image with tag 0");
+    VO_REQUIRE(opt->max_corners >= 1 && (int64_t)opt->max_corners <= (int64_t)h * w, VO_ERR_ARG,
+               "vo_good_features: max_corners %d outside 1..h*w", opt->max_corners);
+    VO_REQUIRE(opt->block_radius >= 1 && opt->block_radius <= 3, VO_ERR_ARG,
+               "vo_good_features: block_radius %d outside 1..3", opt->block_radius);
+    VO_REQUIRE(std::isfinite(opt->quality) && opt->quality > 0.f && opt->quality <= 1.f, VO_ERR_ARG,
+               "vo_good_features: quality must be finite, > 0 and <= 1");
+    VO_REQUIRE(std::isfinite(opt->min_distance) && opt->min_distance >= 0.f && opt->min_distance <= 1024.f, VO_ERR_ARG,
+               "vo_good_features: min_distance must be finite and in 0..1024");
+    VO_REQUIRE(opt->flags == 0, VO_ERR_ARG, "vo_good_features: unknown flags 0x%x", opt->flags);
+    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "vo_good_features: reserved must be 0");
+    *n_out = 0;
+    if (h < 3 || w < 3) return;  // no interior pixel: no corners
+    vo::bind(ctx);
+    vo::good_features_host(ctx, img, tag, h, w, mask, keep, n_keep, opt, corners, resp, n_out);
+  });
+}
+
+int vo_corner_response(vo_ctx* ctx, const uint8_t* img, int h, int w, int block_radius, float* out) {
+  return guarded([&] {
+    VO_REQUIRE(img && out, VO_ERR_ARG, "vo_corner_response: null image or output");
+    VO_REQUIRE(h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)1 << 30, VO_ERR_ARG,
+               "vo_corner_response: bad shape h=%d w=%d", h, w);
+    VO_REQUIRE(block_radius >= 1 && block_radius <= 3, VO_ERR_ARG, "vo_corner_response: block_radius %d outside 1..3",
+               block_radius);
+    vo::bind(ctx);
+    vo::corner_response_host(ctx, img, h, w, block_radius, out);
+  });
+}
+
+int vo_corner_select(vo_ctx* ctx, const int32_t* xy, const float* resp, int n, const float* keep, int n_keep,
+                     float min_distance, int max_corners, int32_t* out_idx, int32_t* n_out) {
+  return guarded([&] {
+    VO_REQUIRE(out_idx && n_out, VO_ERR_ARG, "vo_corner_select: null outputs");
+    VO_REQUIRE(n >= 0 && n_keep >= 0, VO_ERR_ARG, "vo_corner_select: negative count n=%d n_keep=%d", n, n_keep);
+    VO_REQUIRE(n == 0 || (xy && resp), VO_ERR_ARG, "vo_corner_select: null candidates with n > 0");
+    VO_REQUIRE(n_keep == 0 || keep, VO_ERR_ARG, "vo_corner_select: null keep with n_keep > 0");
+    VO_REQUIRE(std::isfinite(min_distance) && min_distance >= 0.f && min_distance <= 1024.f, VO_ERR_ARG,
+               "vo_corner_select: min_distance must be finite and in 0..1024");
+    VO_REQUIRE(max_corners >= 1, VO_ERR_ARG, "vo_corner_select: max_corners %d below 1", max_corners);
+    for (int i = 0; i < n; ++i) {
+      VO_REQUIRE(std::isfinite(resp[i]), VO_ERR_ARG, "vo_corner_select: resp[%d] is not finite", i);
+      VO_REQUIRE(std::abs((int64_t)xy[2 * (size_t)i]) <= (1 << 24) && std::abs((int64_t)xy[2 * (size_t)i + 1]) <= (1 << 24),
+                 VO_ERR_ARG, "vo_corner_select: coordinates of row %d outside +-2^24", i);
+    }
+    *n_out = 0;
+    if (n == 0) return;
+    vo::bind(ctx);
+    vo::corner_select_host(ctx, xy, resp, n, keep, n_keep, min_distance, max_corners, out_idx, n_out);
+  });
+}
+
+int vo_corner_stats(vo_ctx* ctx, int32_t out[4]) {
+  return guarded([&] {
+    VO_REQUIRE(ctx && out, VO_ERR_ARG, "vo_corner_stats: null arguments");
+    vo::corner_stats(ctx, out);
+  });
+}
+
 int vo_sift_detect(vo_ctx* ctx, const uint8_t* img, int h, int w, double contrast, double edge, double sigma,
                    int n_layers, int capacity, float* kp_f, int32_t* kp_i, int32_t* count) {
   return guarded([&] {

@@ -119,6 +119,21 @@ struct KltWorkspace {
   uint64_t clock = 0;
 };
 
+// Corner detector workspace (corners.hip).
+struct CornerWorkspace {
+  DevBuf img, mask;  // host-call staging: an untagged (or uncached) image, the mask
+  DevBuf resp;       // float (h, w) response map
+  DevBuf keys;       // uint64 candidate keys, unsorted then sorted
+  DevBuf sort_tmp;   // rocprim temporary storage
+  DevBuf xy;         // vo_corner_select: the caller's int32 (n, 2) coordinates
+  DevBuf cand;       // per sorted candidate: x, y, id, response, state, next in its cell
+  DevBuf grid;       // int32 list heads per cell: candidates, keep-away points
+  DevBuf keep;       // keep-away points (n_keep, 2) and their next links
+  DevBuf out;        // accepted corners: xy, response, id
+  DevBuf ctl;        // control words (maximum, counts, rounds)
+  int32_t stats[4] = {0, 0, 0, 0};  // the last call's candidates, rounds, accepted, cell side
+};
+
 class BAEngine;   // ba_engine.hip
 struct Comm;      // ba_comm.h (RCCL communicator or loopback group)
 
@@ -156,6 +171,7 @@ struct vo_ctx {
   vo::EssWorkspace ess;
   vo::SiftWorkspace sift;
   vo::KltWorkspace klt;
+  vo::CornerWorkspace corners;
   vo::Profiler prof;
   std::unique_ptr<vo::BAEngine> ba;
   std::unique_ptr<vo::Comm> comm;
@@ -220,6 +236,14 @@ void klt_track_host(vo_ctx* ctx, const uint8_t* img0, uint64_t tag0, const uint8
 void klt_pyramid_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int levels, uint8_t* out, int64_t cap,
                       int32_t* levels_out);
 int klt_layout(int h, int w, int levels, int win_radius, int64_t* out, int n);
+// Corner detector (corners.hip): host arrays, synchronous; the arguments are checked by the caller.
+void good_features_host(vo_ctx* ctx, const uint8_t* img, uint64_t tag, int h, int w, const uint8_t* mask,
+                        const float* keep, int n_keep, const vo_corner_options* opt, float* corners, float* resp,
+                        int32_t* n_out);
+void corner_response_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int block_radius, float* out);
+void corner_select_host(vo_ctx* ctx, const int32_t* xy, const float* resp, int n, const float* keep, int n_keep,
+                        float min_distance, int max_corners, int32_t* out_idx, int32_t* n_out);
+void corner_stats(vo_ctx* ctx, int32_t out[4]);
 // SIFT detection (sift.hip): device images, device keypoint outputs (unsorted).
 void sift_run(vo_ctx* ctx, const uint8_t* d_img, int batch, int h, int w, double contrast, double edge,
               double sigma, int n_layers, int capacity, float* d_kpf, int32_t* d_kpi, int32_t* d_count,

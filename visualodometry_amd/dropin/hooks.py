@@ -34,6 +34,9 @@ are the caller's environment):
   tracked frame brings (:func:`klt_pairs`), and a new keyframe is replenished by detection away
   from its tracked keypoints (:func:`klt_replenish`).  The settings are read once, when the
   frontend is constructed; a frontend without the route reads no ``klt_*`` setting on the frame path.
+  With ``cfg.klt_corner_replenish`` (off by default) the replenishment takes Shi-Tomasi corners
+  (:func:`visualodometry_amd.corners.good_features`) instead of SIFT detections; their rows have no
+  descriptor (a per-row flag says so) and a detected frame is matched against the others only.
 
 The reference keeps only the current keyframe's observation of a freshly
 triangulated point (``vo.py:277-284``); the window also records the previous
@@ -433,6 +436,7 @@ def epipolar_search(vo, prev, curr_feats, curr_ids, ref_indices, curr_indices):
 # keyframe row of each of its rows.
 _KLT_IMAGE, _KLT_TAG, _KLT_SRC, _KLT_SRC_IDX = "_vo_amd_klt_image", "_vo_amd_klt_tag", "_vo_amd_klt_src", \
     "_vo_amd_klt_src_idx"
+_KLT_HAS_DESC = "_vo_amd_klt_has_desc"  # cfg.klt_corner_replenish: (N,) bool, which rows carry a real descriptor
 _klt_tags = itertools.count(1 << 40)  # pyramid-cache tags of the frames seen (one per image, never reused)
 
 
@@ -449,6 +453,14 @@ class KltTracker:
         self.min_tracks = int(getattr(config, "klt_min_tracks", 50))
         self.min_distance = float(getattr(config, "klt_min_distance", 8.0))
         self.max_rows = int(getattr(config, "sift_n_features", 0) or 0)
+        self.corners = bool(getattr(config, "klt_corner_replenish", False))
+        if self.corners:  # (off: neither setting is read)
+            self.corner_quality = float(getattr(config, "klt_corner_quality", 0.01))
+            self.corner_block = int(getattr(config, "klt_corner_block", 3))
+            for other in ("map_reobserve", "map_epipolar_search"):
+                if getattr(config, other, False):
+                    raise ValueError(f"klt_corner_replenish cannot be combined with {other}: that search reads "
+                                     "descriptors of keyframe rows, and a corner's row has none")
         self.owner = None  # weakref to the VisualOdometry (set by its wrapped __init__)
         self.reset()
 
@@ -520,6 +532,8 @@ def klt_process_image(st: KltTracker, img, detect):
     }
     if "image_size" in src:
         feats["image_size"] = src["image_size"]
+    if _KLT_HAS_DESC in src:  # cfg.klt_corner_replenish: the flag follows its descriptor row
+        feats[_KLT_HAS_DESC] = np.asarray(src[_KLT_HAS_DESC], bool)[st.alive]
     return feats
 
 
@@ -568,6 +582,8 @@ def klt_replenish(vo, st: KltTracker, detect) -> int:
     feats = kf.get("feats") if isinstance(kf, dict) else None
     if not isinstance(feats, dict) or feats.get(_KLT_SRC) is None or feats.get(_KLT_IMAGE) is None:
         return 0  # a detected frame is complete already
+    if st.corners:
+        return klt_replenish_corners(vo, st, feats)
     det = detect(feats[_KLT_IMAGE])
     kept = np.asarray(_keypoints(feats), np.float32).reshape(-1, 2)
     new = np.flatnonzero(far_from(kept, _keypoints(det), st.min_distance))
@@ -594,6 +610,77 @@ def klt_replenish(vo, st: KltTracker, detect) -> int:
     kf["feats"] = full
     kf["ids"] = np.concatenate([ids, np.full(new.size, -1, ids.dtype)])
     return int(new.size)
+
+
+def klt_replenish_corners(vo, st: KltTracker, feats: dict) -> int:
+    """:func:`klt_replenish` under ``cfg.klt_corner_replenish``: Shi-Tomasi corners of the keyframe's
+    image (its cached pyramid's level 0), at least ``klt_min_distance`` from every keypoint it has
+    and from each other, as many as ``sift_n_features`` rows leave room for, strongest first.  Their
+    rows get id -1, a zero descriptor and a false flag under ``_KLT_HAS_DESC``."""
+    from .. import corners
+
+    kf = vo.keyframe
+    kept = np.ascontiguousarray(_keypoints(feats), np.float32).reshape(-1, 2)
+    n_kept = len(kept)
+    room = max(st.max_rows - n_kept, 0) if st.max_rows > 0 else None
+    if room == 0:
+        add = np.zeros((0, 2), np.float32)
+    else:
+        add, _ = corners.good_features(feats[_KLT_IMAGE], room, quality=st.corner_quality,
+                                       min_distance=st.min_distance, block_size=st.corner_block, keep=kept,
+                                       tag=feats[_KLT_TAG])
+    kp, des = feats["keypoints"], feats["descriptors"]
+    des_rows = des[0] if getattr(des, "ndim", 2) == 3 else des
+
+    def cat(old, extra):
+        rows = old[0] if getattr(old, "ndim", 2) == 3 else old
+        if hasattr(rows, "detach"):
+            import torch
+
+            out = torch.cat([rows, torch.as_tensor(extra, dtype=rows.dtype, device=rows.device)])
+        else:
+            out = np.concatenate([rows, np.asarray(extra, rows.dtype)])
+        return _batched(out, old)
+
+    had = np.asarray(feats[_KLT_HAS_DESC], bool) if _KLT_HAS_DESC in feats else np.ones(n_kept, bool)
+    full = {k: v for k, v in feats.items() if k not in (_KLT_SRC, _KLT_SRC_IDX)}
+    full["keypoints"] = cat(kp, add)
+    full["descriptors"] = cat(des, np.zeros((len(add), des_rows.shape[1]), np.float32))
+    full[_KLT_HAS_DESC] = np.concatenate([had, np.zeros(len(add), bool)])
+    ids = np.asarray(kf["ids"])
+    kf["feats"] = full
+    kf["ids"] = np.concatenate([ids, np.full(len(add), -1, ids.dtype)])
+    return int(len(add))
+
+
+def klt_descriptor_rows(feats0: dict, feats1: dict, match):
+    """``match_frames`` between dicts of which one has rows without a descriptor
+    (``cfg.klt_corner_replenish``): ``match(sub0, sub1)`` over dicts of the rows that have one, the
+    indices mapped back; an empty (0, 2) array when a side has none.  ``None`` when neither dict is
+    flagged."""
+    flagged = [isinstance(f, dict) and _KLT_HAS_DESC in f for f in (feats0, feats1)]
+    if not any(flagged):
+        return None
+    rows, subs = [], []
+    for f, has in zip((feats0, feats1), flagged):
+        if not has:
+            rows.append(None)
+            subs.append(f)
+            continue
+        idx = np.flatnonzero(np.asarray(f[_KLT_HAS_DESC], bool))
+        if idx.size == 0:
+            return np.zeros((0, 2), np.int64)
+        kp = f["keypoints"]
+        sub = {k: v for k, v in f.items() if not k.startswith("_vo_amd_klt")}
+        sub["keypoints"] = _batched(_rows(kp[0] if getattr(kp, "ndim", 2) == 3 else kp, idx), kp)
+        sub["descriptors"] = _batched(_rows(_descriptors(f), idx), f["descriptors"])
+        rows.append(idx)
+        subs.append(sub)
+    pairs = np.asarray(_np(match(subs[0], subs[1])), np.int64).reshape(-1, 2)
+    for side in (0, 1):
+        if rows[side] is not None:
+            pairs[:, side] = rows[side][pairs[:, side]]
+    return pairs
 
 
 def _detect_as_today(frontend, image):
@@ -767,6 +854,12 @@ def _wrap_match_frames(orig):
             pairs = klt_pairs(feats0, feats1)
             if pairs is not None:
                 return pairs
+            pairs = klt_descriptor_rows(feats0, feats1, lambda a, b: plain(self, a, b))  # cfg.klt_corner_replenish
+            if pairs is not None:
+                return pairs
+        return plain(self, feats0, feats1)
+
+    def plain(self, feats0, feats1):  # the matching without the route
         if getattr(self.conf, "extractor_type", None) == "sift" and getattr(self.conf, "match_on_gpu", True):
             # SIFT integers: the int8 path only, hinted for this call (the context's own hint,
             # which other users of the context may rely on, is restored afterwards)
