@@ -3,7 +3,8 @@ csrc/ba_tables_check.cpp) over windows planned as the engine plans them: the pro
 observation tables against the caller's arrays, K2's output layout for the profile solver and
 the banded solver's one- and two-sided splits (no overlap, inside the system, consistent with the
 plan, ``dense_system`` round trip), the chunk-image runs of a window planned again over its own
-plan, ``reserve_window``, the LM log's layout and decoding.  No GPU needed.
+plan, ``reserve_window``, the LM log's layout and decoding, and ``group_by_point`` on fixed
+inputs.  No GPU needed.
 
 Windows: the smallest that reach every branch -- F = 1 (one-sided only), F = 6 with w = 5
 (one-sided), a mid-sized one, and F = 28 with w = 7 (two-sided) --, each with 1, 3 and 6 chunks
@@ -44,6 +45,14 @@ def check(exe, p, seg_chunks):
         out = subprocess.run([str(exe), fi, str(seg_chunks)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
     return [int(v) for v in out.stdout.split()[1:]]
+
+
+def test_group_by_point(exe):
+    """``group_by_point`` (behind ``vo_ba_group_by_point``) on the check's fixed inputs against its own
+    counting loop: grouped input with empty landmarks, ungrouped input with and without ``order``,
+    out-of-range entries (the first offender is named), ``n_obs = 0``, ``n_points = 0``."""
+    out = subprocess.run([str(exe), "group"], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout == "group ok\n", out.stdout + out.stderr
 
 
 @pytest.mark.parametrize("seg_chunks", [1, 3, 6])

@@ -11,6 +11,8 @@ keypoints in the same order with every field bit for bit, and the descriptors (i
 0..255 stored as float32) identical.
 """
 
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -141,6 +143,39 @@ def test_detect_and_compute_low_contrast_capacity_retry(ctx):
         assert -n > caps[-1] and len(caps) < 3, caps
         caps.append(-n)
     assert len(caps) >= 2 and n == len(ref["pt"]), caps
+
+
+@pytest.fixture(scope="module")
+def textured_small():
+    """A 96 x 128 textured image and the oracle's detectAndCompute of it for nfeatures 0 (116 keypoints) and 50,
+    at contrast 0.02, edge 10."""
+    img = sift_scene(96, 128, seed=41, texture=12.0)
+    return img, {nf: S.detect_and_compute(img, nf, 0.02, 10.0, 1.6) for nf in (0, 50)}
+
+
+@pytest.mark.parametrize("nfeatures", [0, 50])
+def test_detect_and_compute_host_and_device_entries_agree(ctx, textured_small, nfeatures):
+    """``vo_sift_detect_and_compute`` and ``vo_sift_detect_and_compute_dev`` (one host body, the
+    first working capacity and the kind of the final copy apart), each with a capacity of twice
+    the oracle's count: the counts, keypoint records and descriptors are byte-equal between the
+    two entries and equal to the oracle's."""
+    img, refs = textured_small
+    ref = refs[nfeatures]
+    h, w = img.shape
+    cap = 2 * len(ref["pt"])
+    assert cap > 0 and (nfeatures == 0 or len(ref["pt"]) >= nfeatures)
+    kp, desc = sift._detect_and_compute_records(img, nfeatures, 0.02, 10.0, 1.6, 3, cap, ctx)
+    d_kp = _lib.DeviceArray(ctx, (cap, 8), np.int32)
+    d_desc = _lib.DeviceArray(ctx, (cap, 128), np.float32)
+    cnt = C.c_int32(-1)
+    _lib.check(ctx.lib.vo_sift_detect_and_compute_dev(
+        ctx.handle, _lib.ptr(img, C.c_uint8), h, w, nfeatures, 0.02, 10.0, 1.6, 3, cap,
+        C.c_void_p(d_kp.ptr), C.c_void_p(d_desc.ptr), C.byref(cnt)), "vo_sift_detect_and_compute_dev")
+    n = cnt.value
+    assert n == len(kp) == len(ref["pt"])
+    assert d_kp.numpy()[:n].tobytes() == kp.tobytes()
+    assert d_desc.numpy()[:n].tobytes() == desc.tobytes()
+    _check_full(sift._kp_dict(kp, desc), ref)
 
 
 def test_detect_and_compute_edge_cases(ctx):

@@ -1,7 +1,6 @@
 // extern "C" entry points of libvo_hip.so (declared in include/vo_hip.h).
 #include <cstdarg>
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -81,7 +80,6 @@ void bind(vo_ctx* ctx) {
   VO_HIP_CHECK(hipSetDevice(ctx->device));
 }
 
-// Host-array matcher call: descriptors staged into the workspace, results copied back.
 // A caller's device pointer must be device memory of the context's GPU, known to this HIP runtime,
 // whose allocation covers [p, p + bytes).
 void check_device_range(vo_ctx* ctx, const void* p, size_t bytes, const char* what) {
@@ -98,85 +96,6 @@ void check_device_range(vo_ctx* ctx, const void* p, size_t bytes, const char* wh
   if (e2 != hipSuccess) (void)hipGetLastError();
   VO_REQUIRE(e2 == hipSuccess && (const char*)p + bytes <= (const char*)base + size, VO_ERR_ARG,
              "%s: %zu bytes past its allocation", what, bytes);
-}
-
-void match_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
-                double ratio, int32_t* pairs, int32_t* count, int32_t* idx2, float* dist2, uint64_t q_tag = 0,
-                bool device_src = false, bool mutual = false) {
-  VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "match: bad shape n0=%d n1=%d dim=%d",
-             n0, n1, dim);
-  VO_REQUIRE((n0 == 0 || des0) && (n1 == 0 || des1), VO_ERR_ARG, "match: null descriptors");
-  if (count) *count = 0;
-  if (n0 == 0) return;
-  hipStream_t st = ctx->stream;
-  MatchWorkspace& ws = ctx->match;
-  MatchQueryCache& qc = ctx->match_q;
-  // the query side's cache (a nonzero tag; the int8 path's dimensions): a hit skips the query's
-  // upload and packing, a miss packs it into the cache first
-  const bool use_cache = q_tag != 0 && n1 > 0 && dim <= 256;
-  const bool hit = use_cache && qc.valid && qc.tag == q_tag && qc.src == (const void*)des0 && qc.n0 == n0 &&
-                   qc.dim == dim && qc.device_src == device_src;
-  const size_t b0 = (size_t)n0 * dim * 4, b1 = (size_t)n1 * dim * 4;
-  const float* d0 = des0;
-  const float* d1 = des1;
-  if (!device_src) {
-    ws.des.reserve((use_cache ? 0 : b0) + b1 + 16);
-    float* stage1 = ws.des.as<float>() + (use_cache ? 0 : (size_t)n0 * dim);
-    if (use_cache) {
-      if (!hit) {
-        qc.des.reserve(b0);
-        VO_HIP_CHECK(hipMemcpyAsync(qc.des.ptr, des0, b0, hipMemcpyHostToDevice, st));
-      }
-      d0 = qc.des.as<float>();
-    } else {
-      VO_HIP_CHECK(hipMemcpyAsync(ws.des.ptr, des0, b0, hipMemcpyHostToDevice, st));
-      d0 = ws.des.as<float>();
-    }
-    if (n1) VO_HIP_CHECK(hipMemcpyAsync(stage1, des1, b1, hipMemcpyHostToDevice, st));
-    d1 = stage1;
-  }
-  if (use_cache && !hit) {
-    qc.valid = false;
-    match_pack_query(ctx, d0, n0, dim, qc);
-    qc.tag = q_tag;
-    qc.src = des0;
-    qc.n0 = n0;
-    qc.dim = dim;
-    qc.device_src = device_src;
-    qc.valid = true;
-  }
-  ws.best.reserve((size_t)n0 * 4);
-  int32_t* d_idx2 = nullptr;
-  float* d_dist2 = nullptr;
-  if (idx2) {
-    ws.top2.reserve((size_t)n0 * 16);
-    d_idx2 = ws.top2.as<int32_t>();
-    d_dist2 = reinterpret_cast<float*>(d_idx2 + 2 * (size_t)n0);
-  }
-  // the cross check: the reverse pass's nearest query per train row, then the filter over best
-  int32_t* d_rev = nullptr;
-  if (mutual && n1 > 0) {
-    ws.rev.reserve((size_t)n1 * 4);
-    d_rev = ws.rev.as<int32_t>();
-  }
-  match_run(ctx, d0, d1, 1, n0, n1, dim, ratio, ws.best.as<int32_t>(), d_idx2, d_dist2, use_cache ? &qc : nullptr,
-            d_rev);
-  if (d_rev) mutual_filter(ctx, ws.best.as<int32_t>(), d_rev, 1, n0, n1);
-  if (pairs) {
-    ws.pairs.reserve((size_t)n0 * 8 + 16);
-    int32_t* d_pairs = ws.pairs.as<int32_t>();
-    int32_t* d_count = d_pairs + 2 * (size_t)n0;
-    compact_pairs(ctx, ws.best.as<int32_t>(), n0, d_pairs, d_count);
-    // the count and all n0 pair slots (out_pairs' capacity; the slots past the count are left
-    // unspecified) in one round trip: 8 n0 bytes more over PCIe instead of a second sync
-    VO_HIP_CHECK(hipMemcpyAsync(count, d_count, 4, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipMemcpyAsync(pairs, d_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
-  }
-  if (idx2) {
-    VO_HIP_CHECK(hipMemcpyAsync(idx2, d_idx2, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipMemcpyAsync(dist2, d_dist2, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
-  }
-  VO_HIP_CHECK(hipStreamSynchronize(st));
 }
 
 }  // namespace
@@ -198,6 +117,47 @@ static int ba_call(vo_ctx* ctx, uint64_t session, F&& f, const char* arg_error =
     else rc = f();
   });
   return g != VO_OK ? g : rc;
+}
+
+// vo_match_gated and vo_match_segment: one contract but for the gate.  The checks of either
+// entry's options struct (they need no device, nor a context) and the fields the two share; the
+// entry adds its per-query array (pred: 2 floats a query, seg: 4).
+template <class Options>
+static vo::GateHostArgs gate_options(const char* fn, int n0, int n1, int dim, const Options* opt,
+                                     const int32_t* out_pairs, const int32_t* out_count) {
+  VO_REQUIRE(opt && out_pairs && out_count, VO_ERR_ARG, "%s: null options or outputs", fn);
+  VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "%s: bad shape n0=%d n1=%d dim=%d", fn, n0, n1, dim);
+  VO_REQUIRE((opt->flags & ~(VO_MATCH_DEVICE_PTRS | VO_MATCH_GATE_UNIQUE)) == 0, VO_ERR_ARG,
+             "%s: unknown flags 0x%x", fn, opt->flags);
+  VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "%s: reserved must be 0", fn);
+  VO_REQUIRE(std::isfinite(opt->ratio) && opt->ratio >= 0.0 && std::isfinite(opt->max_dist) && opt->max_dist >= 0.0,
+             VO_ERR_ARG, "%s: ratio and max_dist must be finite and >= 0", fn);
+  vo::GateHostArgs g{};
+  g.radius = opt->radius;
+  g.kp1 = opt->kp1;
+  g.radius0 = opt->radius0;
+  g.width = opt->width;
+  g.height = opt->height;
+  g.ratio = opt->ratio;
+  g.max_dist = opt->max_dist;
+  g.unique = (opt->flags & VO_MATCH_GATE_UNIQUE) != 0;
+  g.dev = (opt->flags & VO_MATCH_DEVICE_PTRS) != 0;
+  return g;
+}
+
+// The rest of the two entries: the arrays' checks, then the context and the device ranges.
+static void gate_call(const char* fn, vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                      const vo::GateHostArgs& g, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
+  VO_REQUIRE((n0 == 0 || (des0 && g.query)) && (n1 == 0 || (des1 && g.kp1)), VO_ERR_ARG,
+             "%s: null array with a nonzero size", fn);
+  vo::bind(ctx);
+  if (g.dev) {  // as vo_match_knn2_ratio_dev: refused before any launch
+    vo::check_device_range(ctx, des1, (size_t)n1 * dim * 4, "des1");
+    vo::check_device_range(ctx, g.kp1, (size_t)n1 * 8, "kp1");
+  }
+  *out_count = 0;
+  if (n0 == 0 || n1 == 0) return;
+  vo::match_gate_host(ctx, des0, n0, des1, n1, dim, g, out_pairs, out_dist, out_count);
 }
 
 extern "C" {
@@ -327,20 +287,7 @@ int vo_triangulate(vo_ctx* ctx, const double* P1, const double* P2, const double
     VO_REQUIRE(P1 && P2 && T_cw2 && K && n >= 0, VO_ERR_ARG, "vo_triangulate: bad arguments");
     if (n == 0) return;
     VO_REQUIRE(pts1 && pts2 && pts3d_out && mask_out, VO_ERR_ARG, "vo_triangulate: null arrays");
-    const size_t in = (size_t)n * 2 * sizeof(float), out3 = (size_t)n * 3 * sizeof(float);
-    ctx->match.tri.reserve(2 * in + out3 + (size_t)n + 64);
-    char* base = ctx->match.tri.as<char>();
-    float* d1 = reinterpret_cast<float*>(base);
-    float* d2 = reinterpret_cast<float*>(base + in);
-    float* d3 = reinterpret_cast<float*>(base + 2 * in);
-    uint8_t* dm = reinterpret_cast<uint8_t*>(base + 2 * in + out3);
-    hipStream_t st = ctx->stream;
-    VO_HIP_CHECK(hipMemcpyAsync(d1, pts1, in, hipMemcpyHostToDevice, st));
-    VO_HIP_CHECK(hipMemcpyAsync(d2, pts2, in, hipMemcpyHostToDevice, st));
-    vo::tri_run(ctx, P1, P2, T_cw2, K, d1, d2, n, min_depth, max_reproj_err, d3, dm);
-    VO_HIP_CHECK(hipMemcpyAsync(pts3d_out, d3, out3, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipMemcpyAsync(mask_out, dm, (size_t)n, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipStreamSynchronize(st));
+    vo::triangulate_host(ctx, P1, P2, T_cw2, K, pts1, pts2, n, min_depth, max_reproj_err, pts3d_out, mask_out);
   });
 }
 
@@ -367,37 +314,8 @@ int vo_pnp_ransac(vo_ctx* ctx, const float* objpts, const float* imgpts, int n, 
     *success_out = 0;
     for (int k = 0; k < 3; ++k) rvec_out[k] = tvec_out[k] = 0.0;
     if (n == 0) return;
-    // device and page-locked host staging share one layout, X | uv | pose | status | mask: the
-    // points go up in one copy and the results come back in one
-    const size_t bx = (size_t)n * 12, bu = (size_t)n * 8, bp = 64, bm = (size_t)n;
-    const size_t po = (bx + bu + 15) & ~size_t(15), total = po + bp + 16 + bm;
-    vo::DevBuf& st = ctx->pnp.stage;
-    vo::HostBuf& hs = ctx->pnp.hstage;
-    st.reserve(total + 64);
-    hs.reserve(total + 64);
-    char* base = st.as<char>();
-    char* hbase = hs.as<char>();
-    float* dX = reinterpret_cast<float*>(base);
-    float* dU = reinterpret_cast<float*>(base + bx);
-    double* dP = reinterpret_cast<double*>(base + po);
-    int32_t* dS = reinterpret_cast<int32_t*>(base + po + bp);
-    uint8_t* dM = reinterpret_cast<uint8_t*>(dS + 4);
-    hipStream_t s = ctx->stream;
-    std::memcpy(hbase, objpts, bx);
-    std::memcpy(hbase + bx, imgpts, bu);
-    VO_HIP_CHECK(hipMemcpyAsync(base, hbase, bx + bu, hipMemcpyHostToDevice, s));
-    const int32_t offs[2] = {0, n};
-    vo::pnp_run(ctx, dX, dU, offs, 1, K, iterations, reproj_err, confidence, dP, dM, dS);
-    VO_HIP_CHECK(hipMemcpyAsync(hbase + po, dP, total - po, hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipStreamSynchronize(s));
-    const double* pose = reinterpret_cast<const double*>(hbase + po);
-    const int32_t* status = reinterpret_cast<const int32_t*>(hbase + po + bp);
-    std::memcpy(mask_out, hbase + po + bp + 16, bm);
-    for (int k = 0; k < 3; ++k) {
-      rvec_out[k] = pose[k];
-      tvec_out[k] = pose[3 + k];
-    }
-    *success_out = status[0];
+    vo::pnp_ransac_host(ctx, objpts, imgpts, n, K, iterations, reproj_err, confidence, rvec_out, tvec_out, mask_out,
+                        success_out);
   });
 }
 
@@ -565,41 +483,7 @@ int vo_sift_detect(vo_ctx* ctx, const uint8_t* img, int h, int w, double contras
     VO_REQUIRE(img && count && capacity >= 0 && (capacity == 0 || (kp_f && kp_i)), VO_ERR_ARG,
                "vo_sift_detect: bad arguments");
     VO_REQUIRE(h >= 1 && w >= 1, VO_ERR_ARG, "vo_sift_detect: empty image %dx%d", h, w);
-    vo::SiftWorkspace& ws = ctx->sift;
-    const size_t nimg = (size_t)h * w;
-    const size_t cap = (size_t)std::max(capacity, 1);
-    ws.img.reserve(nimg);
-    ws.kp.reserve(cap * 64 + 64);
-    float* dF = ws.kp.as<float>();
-    int32_t* dI = reinterpret_cast<int32_t*>(dF + cap * 8);
-    int32_t* dC = dI + cap * 8;
-    hipStream_t s = ctx->stream;
-    VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, nimg, hipMemcpyHostToDevice, s));
-    vo::sift_run(ctx, ws.img.as<uint8_t>(), 1, h, w, contrast, edge, sigma, n_layers, capacity, dF, dI, dC, nullptr,
-                 nullptr, nullptr);
-    int32_t found = 0;
-    VO_HIP_CHECK(hipMemcpyAsync(&found, dC, 4, hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipStreamSynchronize(s));
-    const int k = std::min(found, capacity);
-    *count = found;
-    if (k == 0) return;
-    std::vector<float> F((size_t)k * 8);
-    std::vector<int32_t> I((size_t)k * 8);
-    VO_HIP_CHECK(hipMemcpyAsync(F.data(), dF, F.size() * 4, hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipMemcpyAsync(I.data(), dI, I.size() * 4, hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipStreamSynchronize(s));
-    // (image, octave, candidate level, candidate row, candidate column): OpenCV's loop order
-    std::vector<int> ord(k);
-    for (int i = 0; i < k; ++i) ord[i] = i;
-    auto key = [&](int i) {
-      const int32_t* q = &I[(size_t)i * 8];
-      return std::array<int64_t, 6>{q[0], q[1] & 255, q[2], q[6], q[7], i};
-    };
-    std::sort(ord.begin(), ord.end(), [&](int a, int b) { return key(a) < key(b); });
-    for (int i = 0; i < k; ++i) {
-      std::memcpy(kp_f + (size_t)i * 8, &F[(size_t)ord[i] * 8], 32);
-      std::memcpy(kp_i + (size_t)i * 8, &I[(size_t)ord[i] * 8], 32);
-    }
+    vo::sift_detect_host(ctx, img, h, w, contrast, edge, sigma, n_layers, capacity, kp_f, kp_i, count);
   });
 }
 
@@ -620,42 +504,8 @@ int vo_sift_pyramid(vo_ctx* ctx, const uint8_t* img, int h, int w, double sigma,
   return guarded([&] {
     vo::bind(ctx);
     VO_REQUIRE(img && g_out && d_out && h >= 1 && w >= 1, VO_ERR_ARG, "vo_sift_pyramid: bad arguments");
-    int64_t lay[3];
-    vo::sift_layout(h, w, n_layers, lay, 3);
-    VO_REQUIRE(g_floats >= lay[1] && d_floats >= lay[2], VO_ERR_ARG,
-               "vo_sift_pyramid: outputs too small (%lld/%lld floats needed)", (long long)lay[1], (long long)lay[2]);
-    vo::SiftWorkspace& ws = ctx->sift;
-    ws.img.reserve((size_t)h * w);
-    ws.kp.reserve(64);
-    hipStream_t s = ctx->stream;
-    VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, (size_t)h * w, hipMemcpyHostToDevice, s));
-    float *G = nullptr, *D = nullptr;
-    vo::sift_run(ctx, ws.img.as<uint8_t>(), 1, h, w, 0.04, 10.0, sigma, n_layers, 0, nullptr, nullptr,
-                 ws.kp.as<int32_t>(), &G, &D, nullptr);
-    VO_HIP_CHECK(hipMemcpyAsync(g_out, G, (size_t)lay[1] * 4, hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipMemcpyAsync(d_out, D, (size_t)lay[2] * 4, hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipStreamSynchronize(s));
+    vo::sift_pyramid_host(ctx, img, h, w, sigma, n_layers, g_out, g_floats, d_out, d_floats);
   });
-}
-
-// detectAndCompute of a device batch: detection into the workspace's candidate list, then
-// orientation / filtering / descriptors into the caller's buffers.
-static void sift_full(vo_ctx* ctx, const uint8_t* d_imgs, int batch, int h, int w, int nfeatures, double contrast,
-               double edge, double sigma, int n_layers, int capacity, vo_sift_keypoint* d_kps, float* d_desc,
-               int32_t* d_counts) {
-  VO_REQUIRE(d_imgs && d_kps && d_desc && d_counts && batch >= 1 && capacity >= 1 && nfeatures >= 0, VO_ERR_ARG,
-             "sift detectAndCompute: bad arguments");
-  vo::SiftWorkspace& ws = ctx->sift;
-  const int cand_cap = (int)std::min<int64_t>((int64_t)batch * capacity, 1 << 24);
-  ws.cand.reserve((size_t)cand_cap * 64 + 64);
-  float* cf = ws.cand.as<float>();
-  int32_t* ci = reinterpret_cast<int32_t*>(cf + (size_t)cand_cap * 8);
-  int32_t* cc = ci + (size_t)cand_cap * 8;
-  float* G = nullptr;
-  vo::sift_run(ctx, d_imgs, batch, h, w, contrast, edge, sigma, n_layers, cand_cap, cf, ci, cc, &G, nullptr,
-               nullptr);
-  vo::sift_describe(ctx, batch, h, w, n_layers, sigma, nfeatures, capacity, cf, ci, cc, cand_cap, G, d_kps, d_desc,
-                    d_counts);
 }
 
 int vo_sift_detect_and_compute(vo_ctx* ctx, const uint8_t* img, int h, int w, int nfeatures, double contrast,
@@ -665,37 +515,8 @@ int vo_sift_detect_and_compute(vo_ctx* ctx, const uint8_t* img, int h, int w, in
     vo::bind(ctx);
     VO_REQUIRE(img && kps && desc && count && capacity >= 1 && h >= 1 && w >= 1, VO_ERR_ARG,
                "vo_sift_detect_and_compute: bad arguments");
-    vo::SiftWorkspace& ws = ctx->sift;
-    const size_t nimg = (size_t)h * w;
-    ws.img.reserve(nimg);
-    hipStream_t s = ctx->stream;
-    VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, nimg, hipMemcpyHostToDevice, s));
-    // The working capacity (oriented keypoints before duplicate removal and retainBest)
-    // starts at the caller's; an overflowing pass reports the capacity it needed (-n) and the
-    // next pass takes that (at least twice the last, at most the kernel limit: OpenCV has no
-    // cap); only the final keypoints must fit the caller's buffers.
-    int cap = std::min(capacity, vo::sift_max_capacity()), n = -1;
-    vo_sift_keypoint* dK = nullptr;
-    float* dD = nullptr;
-    for (;;) {
-      ws.out.reserve((size_t)cap * (sizeof(vo_sift_keypoint) + 128 * sizeof(float)) + 64);
-      dK = ws.out.as<vo_sift_keypoint>();
-      dD = reinterpret_cast<float*>(dK + cap);
-      int32_t* dC = reinterpret_cast<int32_t*>(dD + (size_t)cap * 128);
-      sift_full(ctx, ws.img.as<uint8_t>(), 1, h, w, nfeatures, contrast, edge, sigma, n_layers, cap, dK, dD, dC);
-      VO_HIP_CHECK(hipMemcpyAsync(&n, dC, 4, hipMemcpyDeviceToHost, s));
-      VO_HIP_CHECK(hipStreamSynchronize(s));
-      if (n >= 0 || cap >= vo::sift_max_capacity()) break;
-      cap = (int)std::min<int64_t>(std::max<int64_t>(-(int64_t)n, 2ll * cap), vo::sift_max_capacity());
-    }
-    VO_REQUIRE(n >= 0, VO_ERR_ARG, "vo_sift_detect_and_compute: more than %d keypoints in one image", cap);
-    VO_REQUIRE(n <= capacity, VO_ERR_ARG, "vo_sift_detect_and_compute: %d keypoints exceed capacity=%d", n,
-               capacity);
-    *count = n;
-    if (n == 0) return;
-    VO_HIP_CHECK(hipMemcpyAsync(kps, dK, (size_t)n * sizeof(vo_sift_keypoint), hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipMemcpyAsync(desc, dD, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToHost, s));
-    VO_HIP_CHECK(hipStreamSynchronize(s));
+    vo::sift_detect_and_compute_host(ctx, img, h, w, nfeatures, contrast, edge, sigma, n_layers, capacity, kps, desc,
+                                     count, false, "vo_sift_detect_and_compute");
   });
 }
 
@@ -709,36 +530,8 @@ int vo_sift_detect_and_compute_dev(vo_ctx* ctx, const uint8_t* img, int h, int w
     // the caller's buffers: device memory of this runtime on the context's GPU, capacity entries each
     vo::check_device_range(ctx, d_kps, (size_t)capacity * sizeof(vo_sift_keypoint), "kps");
     vo::check_device_range(ctx, d_desc, (size_t)capacity * 128 * sizeof(float), "desc");
-    vo::SiftWorkspace& ws = ctx->sift;
-    const size_t nimg = (size_t)h * w;
-    ws.img.reserve(nimg);
-    hipStream_t s = ctx->stream;
-    VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, nimg, hipMemcpyHostToDevice, s));
-    // the working capacity and its retries as vo_sift_detect_and_compute's
-    // (before retainBest the oriented keypoints outnumber the output many times: the working
-    // capacity starts at 32768, as the host entry's default buffers do)
-    int cap = std::min(std::max(capacity, 1 << 15), vo::sift_max_capacity()), n = -1;
-    vo_sift_keypoint* dK = nullptr;
-    float* dD = nullptr;
-    for (;;) {
-      ws.out.reserve((size_t)cap * (sizeof(vo_sift_keypoint) + 128 * sizeof(float)) + 64);
-      dK = ws.out.as<vo_sift_keypoint>();
-      dD = reinterpret_cast<float*>(dK + cap);
-      int32_t* dC = reinterpret_cast<int32_t*>(dD + (size_t)cap * 128);
-      sift_full(ctx, ws.img.as<uint8_t>(), 1, h, w, nfeatures, contrast, edge, sigma, n_layers, cap, dK, dD, dC);
-      VO_HIP_CHECK(hipMemcpyAsync(&n, dC, 4, hipMemcpyDeviceToHost, s));
-      VO_HIP_CHECK(hipStreamSynchronize(s));
-      if (n >= 0 || cap >= vo::sift_max_capacity()) break;
-      cap = (int)std::min<int64_t>(std::max<int64_t>(-(int64_t)n, 2ll * cap), vo::sift_max_capacity());
-    }
-    VO_REQUIRE(n >= 0, VO_ERR_ARG, "vo_sift_detect_and_compute_dev: more than %d keypoints in one image", cap);
-    VO_REQUIRE(n <= capacity, VO_ERR_ARG, "vo_sift_detect_and_compute_dev: %d keypoints exceed capacity=%d", n,
-               capacity);
-    *count = n;
-    if (n == 0) return;
-    VO_HIP_CHECK(hipMemcpyAsync(d_kps, dK, (size_t)n * sizeof(vo_sift_keypoint), hipMemcpyDeviceToDevice, s));
-    VO_HIP_CHECK(hipMemcpyAsync(d_desc, dD, (size_t)n * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    VO_HIP_CHECK(hipStreamSynchronize(s));
+    vo::sift_detect_and_compute_host(ctx, img, h, w, nfeatures, contrast, edge, sigma, n_layers, capacity, d_kps, d_desc,
+                                     count, true, "vo_sift_detect_and_compute_dev");
   });
 }
 
@@ -748,8 +541,8 @@ int vo_sift_detect_and_compute_batch_async(vo_ctx* ctx, const uint8_t* d_imgs, i
                                            int32_t* d_counts) {
   return guarded([&] {
     vo::bind(ctx);
-    sift_full(ctx, d_imgs, batch, h, w, nfeatures, contrast, edge, sigma, n_layers, capacity, d_kps, d_desc,
-              d_counts);
+    vo::sift_detect_and_compute_run(ctx, d_imgs, batch, h, w, nfeatures, contrast, edge, sigma, n_layers, capacity, d_kps,
+                                    d_desc, d_counts);
   });
 }
 
@@ -795,110 +588,24 @@ int vo_match_mutual(vo_ctx* ctx, const float* des0, int n0, uint64_t des0_tag, c
   });
 }
 
-// vo_match_gated and vo_match_segment: one contract but for the gate.  `opt` is either entry's
-// options struct: the two differ in the name and the width of the per-query array (pred: 2 floats,
-// seg: 4), which `gate_of` reads out.
-extern "C++" {
-struct GateOf {
-  const float* query;
-  int qcols;  // 2: predicted position (circular gate); 4: segment a, b (capsule gate)
-};
-static GateOf gate_of(const vo_match_gate_options* o) { return {o->pred, 2}; }
-static GateOf gate_of(const vo_match_segment_options* o) { return {o->seg, 4}; }
-
-template <class Options>
-static int match_gate_entry(const char* fn, vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
-                            const Options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
-  return guarded([&] {
-    // the arguments' own checks first: they need no device (nor a context)
-    VO_REQUIRE(opt && out_pairs && out_count, VO_ERR_ARG, "%s: null options or outputs", fn);
-    VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "%s: bad shape n0=%d n1=%d dim=%d", fn, n0, n1, dim);
-    VO_REQUIRE((opt->flags & ~(VO_MATCH_DEVICE_PTRS | VO_MATCH_GATE_UNIQUE)) == 0, VO_ERR_ARG,
-               "%s: unknown flags 0x%x", fn, opt->flags);
-    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "%s: reserved must be 0", fn);
-    VO_REQUIRE(std::isfinite(opt->ratio) && opt->ratio >= 0.0 && std::isfinite(opt->max_dist) && opt->max_dist >= 0.0,
-               VO_ERR_ARG, "%s: ratio and max_dist must be finite and >= 0", fn);
-    const GateOf gate = gate_of(opt);
-    const size_t qrow = (size_t)gate.qcols * 4;  // bytes per query of the gate's array
-    VO_REQUIRE((n0 == 0 || (des0 && gate.query)) && (n1 == 0 || (des1 && opt->kp1)), VO_ERR_ARG,
-               "%s: null array with a nonzero size", fn);
-    vo::bind(ctx);
-    const bool dev = (opt->flags & VO_MATCH_DEVICE_PTRS) != 0;
-    if (dev) {  // as vo_match_knn2_ratio_dev: refused before any launch
-      vo::check_device_range(ctx, des1, (size_t)n1 * dim * 4, "des1");
-      vo::check_device_range(ctx, opt->kp1, (size_t)n1 * 8, "kp1");
-    }
-    *out_count = 0;
-    if (n0 == 0 || n1 == 0) return;
-    hipStream_t st = ctx->stream;
-    vo::MatchWorkspace& ws = ctx->match;
-    auto a16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    // descriptors: des0 | des1 (host train rows), each 16-byte aligned for the float4 loads
-    const size_t b0 = a16((size_t)n0 * dim * 4), b1 = (size_t)n1 * dim * 4;
-    ws.des.reserve(b0 + (dev ? 0 : b1) + 16);
-    float* d0 = ws.des.as<float>();
-    const float* d1 = des1;
-    VO_HIP_CHECK(hipMemcpyAsync(d0, des0, (size_t)n0 * dim * 4, hipMemcpyHostToDevice, st));
-    if (!dev) {
-      float* s1 = reinterpret_cast<float*>(ws.des.as<char>() + b0);
-      VO_HIP_CHECK(hipMemcpyAsync(s1, des1, b1, hipMemcpyHostToDevice, st));
-      d1 = s1;
-    }
-    // gate workspace: pred or seg | radius | kp1 (host keypoints) | dist | the grid's scratch
-    const size_t bp = a16((size_t)n0 * qrow), br = a16((size_t)n0 * 4), bk = dev ? 0 : a16((size_t)n1 * 8);
-    ws.gate.reserve(bp + br + bk + br + vo::gate_scratch_bytes(n1, opt->width, opt->height));
-    char* gb = ws.gate.as<char>();
-    float* d_pred = reinterpret_cast<float*>(gb);
-    float* d_rad = reinterpret_cast<float*>(gb + bp);
-    float* d_kp = reinterpret_cast<float*>(gb + bp + br);
-    float* d_dist = reinterpret_cast<float*>(gb + bp + br + bk);
-    VO_HIP_CHECK(hipMemcpyAsync(d_pred, gate.query, (size_t)n0 * qrow, hipMemcpyHostToDevice, st));
-    if (opt->radius) VO_HIP_CHECK(hipMemcpyAsync(d_rad, opt->radius, (size_t)n0 * 4, hipMemcpyHostToDevice, st));
-    if (!dev) VO_HIP_CHECK(hipMemcpyAsync(d_kp, opt->kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
-    ws.best.reserve((size_t)n0 * 4);
-    vo::GateArgs g{};
-    g.des0 = d0;
-    g.des1 = d1;
-    g.pred = d_pred;
-    g.radius = opt->radius ? d_rad : nullptr;
-    g.kp1 = dev ? opt->kp1 : d_kp;
-    g.radius0 = opt->radius0;
-    g.n0 = n0;
-    g.n1 = n1;
-    g.dim = dim;
-    g.width = opt->width;
-    g.height = opt->height;
-    g.ratio = opt->ratio;
-    g.max_dist = opt->max_dist;
-    g.unique = (opt->flags & VO_MATCH_GATE_UNIQUE) != 0;
-    g.segment = gate.qcols == 4;
-    g.best = ws.best.as<int32_t>();
-    g.dist = d_dist;
-    vo::gate_run(ctx, g, gb + bp + br + bk + br);
-    ws.pairs.reserve((size_t)n0 * 8 + 16);
-    int32_t* d_pairs = ws.pairs.as<int32_t>();
-    int32_t* d_count = d_pairs + 2 * (size_t)n0;
-    vo::compact_pairs(ctx, g.best, n0, d_pairs, d_count);
-    std::vector<float> dist_q(out_dist ? (size_t)n0 : 0);
-    VO_HIP_CHECK(hipMemcpyAsync(out_count, d_count, 4, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipMemcpyAsync(out_pairs, d_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
-    if (out_dist) VO_HIP_CHECK(hipMemcpyAsync(dist_q.data(), d_dist, (size_t)n0 * 4, hipMemcpyDeviceToHost, st));
-    VO_HIP_CHECK(hipStreamSynchronize(st));
-    // dist1 per pair: the per-query distances gathered in the pairs' order
-    if (out_dist)
-      for (int m = 0; m < *out_count; ++m) out_dist[m] = dist_q[out_pairs[2 * (size_t)m]];
-  });
-}
-}  // extern "C++"
-
 int vo_match_gated(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
                    const vo_match_gate_options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
-  return match_gate_entry("vo_match_gated", ctx, des0, n0, des1, n1, dim, opt, out_pairs, out_dist, out_count);
+  return guarded([&] {
+    vo::GateHostArgs g = gate_options("vo_match_gated", n0, n1, dim, opt, out_pairs, out_count);
+    g.query = opt->pred;
+    g.qcols = 2;
+    gate_call("vo_match_gated", ctx, des0, n0, des1, n1, dim, g, out_pairs, out_dist, out_count);
+  });
 }
 
 int vo_match_segment(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
                      const vo_match_segment_options* opt, int32_t* out_pairs, float* out_dist, int32_t* out_count) {
-  return match_gate_entry("vo_match_segment", ctx, des0, n0, des1, n1, dim, opt, out_pairs, out_dist, out_count);
+  return guarded([&] {
+    vo::GateHostArgs g = gate_options("vo_match_segment", n0, n1, dim, opt, out_pairs, out_count);
+    g.query = opt->seg;
+    g.qcols = 4;
+    gate_call("vo_match_segment", ctx, des0, n0, des1, n1, dim, g, out_pairs, out_dist, out_count);
+  });
 }
 
 int vo_match_mutual_batch_async(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0, int n1,
@@ -908,13 +615,7 @@ int vo_match_mutual_batch_async(vo_ctx* ctx, const float* d_des0, const float* d
     VO_REQUIRE(d_best && (n0 == 0 || d_des0) && (n1 == 0 || d_des1), VO_ERR_ARG,
                "vo_match_mutual_batch_async: null pointers");
     VO_REQUIRE(batch >= 1 && n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "vo_match_mutual_batch_async: bad shape");
-    int32_t* d_rev = nullptr;
-    if (n0 > 0 && n1 > 0) {
-      ctx->match.rev.reserve((size_t)batch * n1 * 4);
-      d_rev = ctx->match.rev.as<int32_t>();
-    }
-    vo::match_run(ctx, d_des0, d_des1, batch, n0, n1, dim, ratio, d_best, nullptr, nullptr, nullptr, d_rev);
-    if (d_rev) vo::mutual_filter(ctx, d_best, d_rev, batch, n0, n1);
+    vo::match_mutual_batch(ctx, d_des0, d_des1, batch, n0, n1, dim, ratio, d_best);
   });
 }
 
@@ -1109,13 +810,9 @@ int vo_ba_debug_stamps(vo_ctx* ctx, uint64_t* out, int n) {
 int vo_ba_plan_digest(const vo_ba_problem* prob, int target_segments, uint64_t* digest) {
   return guarded([&] {
     VO_REQUIRE(prob && digest, VO_ERR_ARG, "vo_ba_plan_digest: null argument");
-    std::vector<int32_t> zero(1, 0);
     vo::BAPlan P;
-    std::string err = vo::build_plan(P, prob->n_poses, prob->n_points, prob->n_obs, prob->n_fixed,
-                                     prob->n_points ? prob->point_ptr : zero.data(), prob->obs_cam,
-                                     prob->obs_uv, vo::seg_obs_for(prob->n_obs, target_segments));
+    const std::string err = vo::plan_window(P, prob, vo::seg_obs_for(prob->n_obs, target_segments));
     VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_plan_digest: %s", err.c_str());
-    vo::build_profile(P, vo::local_profile_first(P));
     *digest = vo::plan_digest(P);
   });
 }
@@ -1124,67 +821,20 @@ int vo_ba_testing_plan_slide(const vo_ba_problem* prev, const vo_ba_problem* cur
                              uint64_t* digest, int64_t* reused_chunks) {
   return guarded([&] {
     VO_REQUIRE(cur && digest && seg_obs >= 1, VO_ERR_ARG, "vo_ba_testing_plan_slide: bad argument");
-    std::vector<int32_t> zero(1, 0);
     vo::BAPlan A, B;
-    auto build = [&](vo::BAPlan& P, const vo_ba_problem* p, const vo::BAPlan* from) {
-      std::string err = vo::build_plan(P, p->n_poses, p->n_points, p->n_obs, p->n_fixed,
-                                       p->n_points ? p->point_ptr : zero.data(), p->obs_cam, p->obs_uv, seg_obs, from,
-                                       seg_chunks);
-      VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_testing_plan_slide: %s", err.c_str());
-      vo::build_profile(P, vo::local_profile_first(P));
-    };
-    if (prev) build(A, prev, nullptr);
-    build(B, cur, prev ? &A : nullptr);
+    std::string err = prev ? vo::plan_window(A, prev, seg_obs, nullptr, seg_chunks) : "";
+    if (err.empty()) err = vo::plan_window(B, cur, seg_obs, prev ? &A : nullptr, seg_chunks);
+    VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_testing_plan_slide: %s", err.c_str());
     *digest = vo::plan_digest(B);
     if (reused_chunks) *reused_chunks = B.reused_chunks;
   });
 }
 
 int vo_ba_group_by_point(int n_points, int n_obs, const int32_t* obs_pt, int32_t* order, int32_t* point_ptr) {
-  int grouped = 1;
+  bool grouped = true;
   const int rc = guarded([&] {
-    VO_REQUIRE(n_points >= 0 && n_obs >= 0, VO_ERR_ARG, "vo_ba_group_by_point: bad sizes");
-    VO_REQUIRE(point_ptr && (n_obs == 0 || obs_pt), VO_ERR_ARG, "vo_ba_group_by_point: null argument");
-    if (!order) {  // already grouped (nondecreasing obs_pt)?  then only point_ptr
-      const int32_t* __restrict op = obs_pt;
-      int32_t* __restrict pp = point_ptr;
-      unsigned descending = 0;  // branch-free scan
-      for (int o = 1; o < n_obs; ++o) descending |= op[o] < op[o - 1];
-      // nondecreasing: in range iff the ends are; otherwise every entry is checked
-      unsigned out_of_range = n_obs > 0 && ((unsigned)op[0] >= (unsigned)n_points ||
-                                            (unsigned)op[n_obs - 1] >= (unsigned)n_points);
-      if (descending)
-        for (int o = 0; o < n_obs; ++o) out_of_range |= (unsigned)op[o] >= (unsigned)n_points;
-      if (out_of_range) {
-        int o = 0;
-        while ((unsigned)op[o] < (unsigned)n_points) ++o;
-        VO_REQUIRE(false, VO_ERR_ARG, "vo_ba_group_by_point: obs_pt[%d]=%d out of range", o, op[o]);
-      }
-      if (descending) {
-        grouped = 0;
-        return;
-      }
-      // grouped: landmark p's run starts at its first observation, or (none) where the next
-      // landmark's does.  Branch-free, and no per-observation read-modify-write: the first
-      // observations stored from the back, then a running minimum from the last landmark.
-      std::fill(pp, pp + n_points + 1, n_obs);
-      for (int o = n_obs - 1; o >= 0; --o) pp[op[o]] = o;
-      int run = n_obs;
-      for (int p = n_points - 1; p >= 0; --p) {
-        run = std::min(run, pp[p]);
-        pp[p] = run;
-      }
-      return;
-    }
-    std::fill(point_ptr, point_ptr + n_points + 1, 0);
-    for (int o = 0; o < n_obs; ++o) {
-      VO_REQUIRE(obs_pt[o] >= 0 && obs_pt[o] < n_points, VO_ERR_ARG, "vo_ba_group_by_point: obs_pt[%d]=%d out of range",
-                 o, obs_pt[o]);
-      ++point_ptr[obs_pt[o] + 1];
-    }
-    for (int p = 0; p < n_points; ++p) point_ptr[p + 1] += point_ptr[p];
-    std::vector<int32_t> next(point_ptr, point_ptr + std::max(n_points, 1));
-    for (int o = 0; o < n_obs; ++o) order[next[obs_pt[o]]++] = o;  // stable: caller order within a landmark
+    const std::string err = vo::group_by_point(n_points, n_obs, obs_pt, order, point_ptr, grouped);
+    VO_REQUIRE(err.empty(), VO_ERR_ARG, "%s", err.c_str());
   });
   return rc == VO_OK && !grouped ? 1 : rc;
 }
@@ -1193,13 +843,10 @@ int vo_ba_plan_probe(const vo_ba_problem* prob, int target_segments, int64_t* ou
   int k = 0;
   int g = guarded([&] {
     VO_REQUIRE(prob && out, VO_ERR_ARG, "vo_ba_plan_probe: null argument");
-    std::vector<int32_t> zero(1, 0);
     vo::BAPlan P;
-    std::string err = vo::build_plan(P, prob->n_poses, prob->n_points, prob->n_obs, prob->n_fixed,
-                                     prob->n_points ? prob->point_ptr : zero.data(), prob->obs_cam,
-                                     prob->obs_uv, vo::seg_obs_for(prob->n_obs, target_segments));
+    const std::string err = vo::plan_window(P, prob, vo::seg_obs_for(prob->n_obs, target_segments));
     VO_REQUIRE(err.empty(), VO_ERR_ARG, "vo_ba_plan_probe: %s", err.c_str());
-    vo::build_profile(P, vo::local_profile_first(P));
+    // (the table stays here: the band split is declared in ba_band.h, which needs HIP)
     int64_t max_pairs = 0, max_slots = 0, max_cams = 0;
     for (int c = 0, s = 0; c < P.n_chunks(); ++c) {
       while (s + 1 < P.n_segments() + 1 && P.seg_chunk[s + 1] <= c) ++s;
@@ -1322,15 +969,7 @@ int vo_pnp_testing_last_split(vo_ctx* ctx, int* h1, int* tail_frames) {
   return guarded([&] {
     VO_REQUIRE(ctx != nullptr && h1 && tail_frames, VO_ERR_ARG, "vo_pnp_testing_last_split: bad arguments");
     vo::bind(ctx);
-    vo::PnpWorkspace& ws = ctx->pnp;
-    const int batch = (int)ws.offsets.size() - 1;
-    *h1 = ws.last_h1;
-    *tail_frames = 0;
-    if (batch <= 0 || ws.last_h1 >= ws.H) return;
-    std::vector<int32_t> need(batch);
-    VO_HIP_CHECK(hipMemcpyAsync(need.data(), ws.need.ptr, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, ctx->stream));
-    VO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    for (int v : need) *tail_frames += v != 0;
+    vo::pnp_last_split(ctx, h1, tail_frames);
   });
 }
 

@@ -224,4 +224,64 @@ void factor_lower_first(const FactorRows& R, std::vector<int32_t>& first) {
     }
 }
 
+std::string plan_window(BAPlan& P, const vo_ba_problem* prob, int seg_obs, const BAPlan* prev, int seg_chunks) {
+  const int32_t zero = 0;
+  const std::string err = build_plan(P, prob->n_poses, prob->n_points, prob->n_obs, prob->n_fixed,
+                                     prob->n_points ? prob->point_ptr : &zero, prob->obs_cam, prob->obs_uv, seg_obs, prev,
+                                     seg_chunks);
+  if (err.empty()) build_profile(P, local_profile_first(P));
+  return err;
+}
+
+static std::string obs_pt_error(int o, int32_t p) {
+  return "vo_ba_group_by_point: obs_pt[" + std::to_string(o) + "]=" + std::to_string(p) + " out of range";
+}
+
+std::string group_by_point(int n_points, int n_obs, const int32_t* obs_pt, int32_t* order, int32_t* point_ptr,
+                           bool& grouped) {
+  grouped = true;
+  if (n_points < 0 || n_obs < 0) return "vo_ba_group_by_point: bad sizes";
+  if (!point_ptr || (n_obs != 0 && !obs_pt)) return "vo_ba_group_by_point: null argument";
+  if (!order) {  // already grouped (nondecreasing obs_pt)?  then only point_ptr
+    const int32_t* __restrict op = obs_pt;
+    int32_t* __restrict pp = point_ptr;
+    unsigned descending = 0;  // branch-free scan
+    for (int o = 1; o < n_obs; ++o) descending |= op[o] < op[o - 1];
+    // nondecreasing: in range iff the ends are; otherwise every entry is checked
+    unsigned out_of_range = n_obs > 0 && ((unsigned)op[0] >= (unsigned)n_points ||
+                                          (unsigned)op[n_obs - 1] >= (unsigned)n_points);
+    if (descending)
+      for (int o = 0; o < n_obs; ++o) out_of_range |= (unsigned)op[o] >= (unsigned)n_points;
+    if (out_of_range) {
+      int o = 0;
+      while ((unsigned)op[o] < (unsigned)n_points) ++o;
+      return obs_pt_error(o, op[o]);
+    }
+    if (descending) {
+      grouped = false;
+      return "";
+    }
+    // grouped: landmark p's run starts at its first observation, or (none) where the next
+    // landmark's does.  Branch-free, and no per-observation read-modify-write: the first
+    // observations stored from the back, then a running minimum from the last landmark.
+    std::fill(pp, pp + n_points + 1, n_obs);
+    for (int o = n_obs - 1; o >= 0; --o) pp[op[o]] = o;
+    int run = n_obs;
+    for (int p = n_points - 1; p >= 0; --p) {
+      run = std::min(run, pp[p]);
+      pp[p] = run;
+    }
+    return "";
+  }
+  std::fill(point_ptr, point_ptr + n_points + 1, 0);
+  for (int o = 0; o < n_obs; ++o) {
+    if (obs_pt[o] < 0 || obs_pt[o] >= n_points) return obs_pt_error(o, obs_pt[o]);
+    ++point_ptr[obs_pt[o] + 1];
+  }
+  for (int p = 0; p < n_points; ++p) point_ptr[p + 1] += point_ptr[p];
+  std::vector<int32_t> next(point_ptr, point_ptr + std::max(n_points, 1));
+  for (int o = 0; o < n_obs; ++o) order[next[obs_pt[o]]++] = o;  // stable: caller order within a landmark
+  return "";
+}
+
 }  // namespace vo

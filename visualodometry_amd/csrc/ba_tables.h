@@ -1,6 +1,7 @@
 // The BA engine's host arithmetic (ba_engine.hip): K2's output layout and its inverse, the
 // problem-order tables of the read-outs, the chunk-image runs of a setup, reserve()'s synthetic
-// window, the LM log's layout and vo_ba_run_lm's options.  Host only -- a plan and plain ints in,
+// window, the LM log's layout, vo_ba_run_lm's options, the host-only planning entries' plan and
+// vo_ba_group_by_point's grouping.  Host only -- a plan and plain ints in,
 // plain vectors out, no HIP -- so csrc/ba_tables_check.cpp runs all of it without a GPU
 // (tests/test_ba_tables.py).  The tables are filled in place: the engine keeps them across
 // sessions (their capacity is reused, and some are the sources of asynchronous copies).
@@ -100,5 +101,18 @@ void factor_lower_first(const FactorRows& rows, std::vector<int32_t>& first);
 inline bool factor_marginalised(int cam_i, int cam_j, int n_drop) {
   return cam_i < n_drop || (cam_j >= 0 && cam_j < n_drop);
 }
+
+// A problem planned on the host alone (vo_ba_plan_digest, vo_ba_plan_probe, vo_ba_testing_plan_slide):
+// build_plan, then the profile of the plan's own first[].  Returns build_plan's message, empty if
+// the plan was built.
+std::string plan_window(BAPlan& P, const vo_ba_problem* prob, int seg_obs, const BAPlan* prev = nullptr,
+                        int seg_chunks = 1);
+
+// vo_ba_group_by_point (vo_hip.h): the CSR point_ptr (n_points + 1) of obs_pt and, with order,
+// the stable permutation that groups the observations by landmark.  Without order the input must
+// be grouped already (nondecreasing): grouped tells whether it was, and point_ptr is written only
+// then.  Returns the message of the first bad argument, empty if none.
+std::string group_by_point(int n_points, int n_obs, const int32_t* obs_pt, int32_t* order, int32_t* point_ptr,
+                           bool& grouped);
 
 }  // namespace vo

@@ -15,6 +15,10 @@
 // range behind K1's sources and ahead of the prior's, none twice; the argument checks and the
 // marginalisation's mask rule.  Prints "factors ok <free poses> <bandwidth> <with the chain> <with
 // the far factor> <factor slab rows>".
+// argv[1] "group" (no input file): group_by_point on small fixed inputs against a counting loop --
+// grouped input with empty landmarks at both ends and in the middle, ungrouped input with and
+// without order, out-of-range entries at the first, the last and a middle position, no
+// observations, no landmarks, the argument checks.  Prints "group ok".
 // Prints "ok <free poses> <bandwidth> <layouts checked> <chunks> <chunks taken over>" or the
 // first violation.
 #include <algorithm>
@@ -419,8 +423,67 @@ static bool check_factors(BAPlan& P, int N, int nf) {
   return true;
 }
 
+// group_by_point against a counting loop: with order, the CSR and the stable grouping; without,
+// the CSR of grouped input and the verdict alone (point_ptr untouched) of ungrouped input.
+static bool check_group(int n_points, const std::vector<int32_t>& pt, const char* what) {
+  const int M = (int)pt.size();
+  bool sorted = true;
+  for (int o = 1; o < M; ++o) sorted = sorted && pt[o] >= pt[o - 1];
+  std::vector<int32_t> want_ptr(n_points + 1, 0), want_order;
+  for (int p = 0; p < n_points; ++p) {
+    for (int o = 0; o < M; ++o)
+      if (pt[o] == p) want_order.push_back(o);
+    want_ptr[p + 1] = (int32_t)want_order.size();
+  }
+  const int32_t* in = M ? pt.data() : nullptr;
+  std::vector<int32_t> ptr(n_points + 1, -7), order(std::max(M, 1), -7);
+  bool grouped = false;
+  std::string err = vo::group_by_point(n_points, M, in, order.data(), ptr.data(), grouped);
+  order.resize(M);
+  if (!err.empty() || !grouped || ptr != want_ptr || order != want_order) FAIL("group_by_point, %s, with order: %s", what, err.c_str());
+  ptr.assign(n_points + 1, -7);
+  err = vo::group_by_point(n_points, M, in, nullptr, ptr.data(), grouped);
+  if (!err.empty() || grouped != sorted || ptr != (sorted ? want_ptr : std::vector<int32_t>(n_points + 1, -7)))
+    FAIL("group_by_point, %s, without order: %s", what, err.c_str());
+  return true;
+}
+
+// a bad entry: both paths name the first offender and report nothing else
+static bool check_group_error(int n_points, const std::vector<int32_t>& pt, int at) {
+  const std::string want = "vo_ba_group_by_point: obs_pt[" + std::to_string(at) + "]=" + std::to_string(pt[at]) + " out of range";
+  std::vector<int32_t> ptr(n_points + 1), order(pt.size());
+  for (int32_t* ord : {order.data(), (int32_t*)nullptr}) {
+    bool grouped = false;
+    const std::string err = vo::group_by_point(n_points, (int)pt.size(), pt.data(), ord, ptr.data(), grouped);
+    if (err != want || !grouped) FAIL("group_by_point %s order: \"%s\", not \"%s\"", ord ? "with" : "without", err.c_str(), want.c_str());
+  }
+  return true;
+}
+
+static bool check_group_by_point() {
+  if (!check_group(7, {1, 1, 2, 4, 4, 4, 5}, "grouped, landmarks 0, 3 and 6 empty") ||
+      !check_group(7, {3, 0, 3, 1, 0, 5, 3}, "ungrouped") || !check_group(2, {1, 0}, "ungrouped, two observations") ||
+      !check_group(1, {0, 0, 0}, "one landmark") || !check_group(3, {}, "n_obs = 0") || !check_group(0, {}, "n_points = 0"))
+    return false;
+  // out of range at the first, the last and a middle position, in grouped and ungrouped input
+  if (!check_group_error(3, {9, 1, 2}, 0) || !check_group_error(3, {0, 1, 3}, 2) || !check_group_error(3, {0, -1, 2}, 1) ||
+      !check_group_error(3, {-1, 0, 2}, 0) || !check_group_error(3, {2, 0, 3}, 2) || !check_group_error(3, {2, 7, 0}, 1) ||
+      !check_group_error(4, {0, 7, -2, 1, 9}, 1) || !check_group_error(0, {0}, 0))
+    return false;
+  bool grouped = false;
+  int32_t one[1] = {0}, ptr[2];
+  if (vo::group_by_point(-1, 0, one, nullptr, ptr, grouped) != "vo_ba_group_by_point: bad sizes" ||
+      vo::group_by_point(1, -1, one, nullptr, ptr, grouped) != "vo_ba_group_by_point: bad sizes" ||
+      vo::group_by_point(1, 1, one, nullptr, nullptr, grouped) != "vo_ba_group_by_point: null argument" ||
+      vo::group_by_point(1, 1, nullptr, one, ptr, grouped) != "vo_ba_group_by_point: null argument")
+    FAIL("group_by_point: bad sizes or a null argument accepted");
+  std::printf("group ok\n");
+  return true;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
+  if (std::string(argv[1]) == "group") return check_group_by_point() ? 0 : 1;
   FILE* f = std::fopen(argv[1], "rb");
   if (!f) return 2;
   int32_t hd[5];

@@ -752,7 +752,7 @@ PassShape pass_shape(const vo_ctx* ctx, int batch, int n0, int n1) {
 // (generation 1: [0] = 1 if a value is not an integer in [0, 255], [1] = 1 if one is not finite).
 // Its column constants are kept too: under the cross check the cached side is the reverse
 // pass's columns.
-void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc) {
+static void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc) {
   hipStream_t st = ctx->stream;
   const int Dp = ceil_div(dim, kKStep) * kKStep;
   const int n0_pad = ceil_div(std::max(n0, 1), kRowsPerWG) * kRowsPerWG;
@@ -972,7 +972,7 @@ void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch,
 }
 
 // The cross check's filter over best (batch, n0) with the reverse pass's rev (batch, n1)
-void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch, int n0, int n1) {
+static void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch, int n0, int n1) {
   const int total = batch * n0;
   if (total == 0) return;
   hipLaunchKernelGGL(mutual_filter_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, ctx->stream, d_best, d_rev,
@@ -985,6 +985,98 @@ void compact_pairs(vo_ctx* ctx, const int32_t* d_best, int n0, int32_t* d_pairs,
   hipLaunchKernelGGL(compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_best, n0,
                      d_pairs, d_count);
   VO_HIP_CHECK(hipGetLastError());
+}
+
+// Host-array matcher call: descriptors staged into the workspace, results copied back.
+void match_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                double ratio, int32_t* pairs, int32_t* count, int32_t* idx2, float* dist2, uint64_t q_tag,
+                bool device_src, bool mutual) {
+  VO_REQUIRE(n0 >= 0 && n1 >= 0 && dim >= 1, VO_ERR_ARG, "match: bad shape n0=%d n1=%d dim=%d",
+             n0, n1, dim);
+  VO_REQUIRE((n0 == 0 || des0) && (n1 == 0 || des1), VO_ERR_ARG, "match: null descriptors");
+  if (count) *count = 0;
+  if (n0 == 0) return;
+  hipStream_t st = ctx->stream;
+  MatchWorkspace& ws = ctx->match;
+  MatchQueryCache& qc = ctx->match_q;
+  // the query side's cache (a nonzero tag; the int8 path's dimensions): a hit skips the query's
+  // upload and packing, a miss packs it into the cache first
+  const bool use_cache = q_tag != 0 && n1 > 0 && dim <= 256;
+  const bool hit = use_cache && qc.valid && qc.tag == q_tag && qc.src == (const void*)des0 && qc.n0 == n0 &&
+                   qc.dim == dim && qc.device_src == device_src;
+  const size_t b0 = (size_t)n0 * dim * 4, b1 = (size_t)n1 * dim * 4;
+  const float* d0 = des0;
+  const float* d1 = des1;
+  if (!device_src) {
+    ws.des.reserve((use_cache ? 0 : b0) + b1 + 16);
+    float* stage1 = ws.des.as<float>() + (use_cache ? 0 : (size_t)n0 * dim);
+    if (use_cache) {
+      if (!hit) {
+        qc.des.reserve(b0);
+        VO_HIP_CHECK(hipMemcpyAsync(qc.des.ptr, des0, b0, hipMemcpyHostToDevice, st));
+      }
+      d0 = qc.des.as<float>();
+    } else {
+      VO_HIP_CHECK(hipMemcpyAsync(ws.des.ptr, des0, b0, hipMemcpyHostToDevice, st));
+      d0 = ws.des.as<float>();
+    }
+    if (n1) VO_HIP_CHECK(hipMemcpyAsync(stage1, des1, b1, hipMemcpyHostToDevice, st));
+    d1 = stage1;
+  }
+  if (use_cache && !hit) {
+    qc.valid = false;
+    match_pack_query(ctx, d0, n0, dim, qc);
+    qc.tag = q_tag;
+    qc.src = des0;
+    qc.n0 = n0;
+    qc.dim = dim;
+    qc.device_src = device_src;
+    qc.valid = true;
+  }
+  ws.best.reserve((size_t)n0 * 4);
+  int32_t* d_idx2 = nullptr;
+  float* d_dist2 = nullptr;
+  if (idx2) {
+    ws.top2.reserve((size_t)n0 * 16);
+    d_idx2 = ws.top2.as<int32_t>();
+    d_dist2 = reinterpret_cast<float*>(d_idx2 + 2 * (size_t)n0);
+  }
+  // the cross check: the reverse pass's nearest query per train row, then the filter over best
+  int32_t* d_rev = nullptr;
+  if (mutual && n1 > 0) {
+    ws.rev.reserve((size_t)n1 * 4);
+    d_rev = ws.rev.as<int32_t>();
+  }
+  match_run(ctx, d0, d1, 1, n0, n1, dim, ratio, ws.best.as<int32_t>(), d_idx2, d_dist2, use_cache ? &qc : nullptr,
+            d_rev);
+  if (d_rev) mutual_filter(ctx, ws.best.as<int32_t>(), d_rev, 1, n0, n1);
+  if (pairs) {
+    ws.pairs.reserve((size_t)n0 * 8 + 16);
+    int32_t* d_pairs = ws.pairs.as<int32_t>();
+    int32_t* d_count = d_pairs + 2 * (size_t)n0;
+    compact_pairs(ctx, ws.best.as<int32_t>(), n0, d_pairs, d_count);
+    // the count and all n0 pair slots (out_pairs' capacity; the slots past the count are left
+    // unspecified) in one round trip: 8 n0 bytes more over PCIe instead of a second sync
+    VO_HIP_CHECK(hipMemcpyAsync(count, d_count, 4, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(pairs, d_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (idx2) {
+    VO_HIP_CHECK(hipMemcpyAsync(idx2, d_idx2, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
+    VO_HIP_CHECK(hipMemcpyAsync(dist2, d_dist2, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
+  }
+  VO_HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// The batched cross check on device arrays: the reverse pass into the workspace, then the filter.
+void match_mutual_batch(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0, int n1, int dim,
+                        double ratio, int32_t* d_best) {
+  int32_t* d_rev = nullptr;
+  if (n0 > 0 && n1 > 0) {
+    ctx->match.rev.reserve((size_t)batch * n1 * 4);
+    d_rev = ctx->match.rev.as<int32_t>();
+  }
+  match_run(ctx, d_des0, d_des1, batch, n0, n1, dim, ratio, d_best, nullptr, nullptr, nullptr, d_rev);
+  if (d_rev) mutual_filter(ctx, d_best, d_rev, batch, n0, n1);
 }
 
 }  // namespace vo

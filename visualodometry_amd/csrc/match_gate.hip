@@ -45,6 +45,7 @@
 // trips and not one dependent load chain per row.
 #include <algorithm>
 #include <cfloat>
+#include <vector>
 
 #include "vo_ctx.h"
 
@@ -376,17 +377,33 @@ __global__ __launch_bounds__(256) void gate_unique_kernel(int32_t* __restrict__ 
 
 size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
+// gate_run's device arrays: descriptors, gate and keypoints in, best (n0) and dist (n0) out.
+struct GateArgs {
+  const float* des0;    // (n0, dim)
+  const float* des1;    // (n1, dim)
+  const float* pred;    // (n0, 2); with segment (n0, 4): ax, ay, bx, by
+  const float* radius;  // (n0) or null: radius0
+  const float* kp1;     // (n1, 2)
+  float radius0;
+  int n0, n1, dim, width, height;
+  double ratio, max_dist;
+  bool unique;
+  bool segment;         // the capsule gate of vo_match_segment around pred's segments
+  int32_t* best;        // (n0) kept train row or -1
+  float* dist;          // (n0) dist1 of the kept pair (unspecified where best is -1)
+};
+
 }  // namespace
 
 // scratch: start (ncell + 1) | cursor (ncell) | items (n1) | owner (n1 x u64) | count (ncell): the
 // last two are cleared by one memset
-size_t gate_scratch_bytes(int n1, int width, int height) {
+static size_t gate_scratch_bytes(int n1, int width, int height) {
   const Grid g = grid_shape(width, height);
   const size_t ncell = (size_t)g.gw * g.gh;
   return align16((ncell + 1) * 4) + align16(ncell * 4) + align16((size_t)n1 * 4) + (size_t)n1 * 8 + ncell * 4 + 16;
 }
 
-void gate_run(vo_ctx* ctx, const GateArgs& a, void* scratch) {
+static void gate_run(vo_ctx* ctx, const GateArgs& a, void* scratch) {
   if (a.n0 == 0) return;
   hipStream_t st = ctx->stream;
   const Grid g = grid_shape(a.width, a.height);
@@ -443,6 +460,67 @@ void gate_run(vo_ctx* ctx, const GateArgs& a, void* scratch) {
   if (s.owner) hipLaunchKernelGGL(gate_unique_kernel, dim3(ceil_div(a.n0, 256)), dim3(256), 0, st, a.best, owner, a.n0);
   VO_HIP_CHECK(hipGetLastError());
   ctx->prof.end(st);
+}
+
+void match_gate_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim, const GateHostArgs& h,
+                     int32_t* out_pairs, float* out_dist, int32_t* out_count) {
+  hipStream_t st = ctx->stream;
+  MatchWorkspace& ws = ctx->match;
+  const size_t qrow = (size_t)h.qcols * 4;  // bytes per query of the gate's array
+  // descriptors: des0 | des1 (host train rows), each 16-byte aligned for the float4 loads
+  const size_t b0 = align16((size_t)n0 * dim * 4), b1 = (size_t)n1 * dim * 4;
+  ws.des.reserve(b0 + (h.dev ? 0 : b1) + 16);
+  float* d0 = ws.des.as<float>();
+  const float* d1 = des1;
+  VO_HIP_CHECK(hipMemcpyAsync(d0, des0, (size_t)n0 * dim * 4, hipMemcpyHostToDevice, st));
+  if (!h.dev) {
+    float* s1 = reinterpret_cast<float*>(ws.des.as<char>() + b0);
+    VO_HIP_CHECK(hipMemcpyAsync(s1, des1, b1, hipMemcpyHostToDevice, st));
+    d1 = s1;
+  }
+  // gate workspace: pred or seg | radius | kp1 (host keypoints) | dist | the grid's scratch
+  const size_t bp = align16((size_t)n0 * qrow), br = align16((size_t)n0 * 4), bk = h.dev ? 0 : align16((size_t)n1 * 8);
+  ws.gate.reserve(bp + br + bk + br + gate_scratch_bytes(n1, h.width, h.height));
+  char* gb = ws.gate.as<char>();
+  float* d_pred = reinterpret_cast<float*>(gb);
+  float* d_rad = reinterpret_cast<float*>(gb + bp);
+  float* d_kp = reinterpret_cast<float*>(gb + bp + br);
+  float* d_dist = reinterpret_cast<float*>(gb + bp + br + bk);
+  VO_HIP_CHECK(hipMemcpyAsync(d_pred, h.query, (size_t)n0 * qrow, hipMemcpyHostToDevice, st));
+  if (h.radius) VO_HIP_CHECK(hipMemcpyAsync(d_rad, h.radius, (size_t)n0 * 4, hipMemcpyHostToDevice, st));
+  if (!h.dev) VO_HIP_CHECK(hipMemcpyAsync(d_kp, h.kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
+  ws.best.reserve((size_t)n0 * 4);
+  GateArgs g{};
+  g.des0 = d0;
+  g.des1 = d1;
+  g.pred = d_pred;
+  g.radius = h.radius ? d_rad : nullptr;
+  g.kp1 = h.dev ? h.kp1 : d_kp;
+  g.radius0 = h.radius0;
+  g.n0 = n0;
+  g.n1 = n1;
+  g.dim = dim;
+  g.width = h.width;
+  g.height = h.height;
+  g.ratio = h.ratio;
+  g.max_dist = h.max_dist;
+  g.unique = h.unique;
+  g.segment = h.qcols == 4;
+  g.best = ws.best.as<int32_t>();
+  g.dist = d_dist;
+  gate_run(ctx, g, gb + bp + br + bk + br);
+  ws.pairs.reserve((size_t)n0 * 8 + 16);
+  int32_t* d_pairs = ws.pairs.as<int32_t>();
+  int32_t* d_count = d_pairs + 2 * (size_t)n0;
+  compact_pairs(ctx, g.best, n0, d_pairs, d_count);
+  std::vector<float> dist_q(out_dist ? (size_t)n0 : 0);
+  VO_HIP_CHECK(hipMemcpyAsync(out_count, d_count, 4, hipMemcpyDeviceToHost, st));
+  VO_HIP_CHECK(hipMemcpyAsync(out_pairs, d_pairs, (size_t)n0 * 8, hipMemcpyDeviceToHost, st));
+  if (out_dist) VO_HIP_CHECK(hipMemcpyAsync(dist_q.data(), d_dist, (size_t)n0 * 4, hipMemcpyDeviceToHost, st));
+  VO_HIP_CHECK(hipStreamSynchronize(st));
+  // dist1 per pair: the per-query distances gathered in the pairs' order
+  if (out_dist)
+    for (int m = 0; m < *out_count; ++m) out_dist[m] = dist_q[out_pairs[2 * (size_t)m]];
 }
 
 }  // namespace vo

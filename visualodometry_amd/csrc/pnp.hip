@@ -629,4 +629,52 @@ void pnp_run(vo_ctx* ctx, const float* d_X, const float* d_uv, const int32_t* of
   VO_HIP_CHECK(hipGetLastError());
 }
 
+void pnp_ransac_host(vo_ctx* ctx, const float* objpts, const float* imgpts, int n, const double* K, int iterations,
+                     double reproj_err, double confidence, double* rvec_out, double* tvec_out, uint8_t* mask_out,
+                     int32_t* success_out) {
+  // device and page-locked host staging share one layout, X | uv | pose | status | mask: the
+  // points go up in one copy and the results come back in one
+  const size_t bx = (size_t)n * 12, bu = (size_t)n * 8, bp = 64, bm = (size_t)n;
+  const size_t po = (bx + bu + 15) & ~size_t(15), total = po + bp + 16 + bm;
+  DevBuf& st = ctx->pnp.stage;
+  HostBuf& hs = ctx->pnp.hstage;
+  st.reserve(total + 64);
+  hs.reserve(total + 64);
+  char* base = st.as<char>();
+  char* hbase = hs.as<char>();
+  float* dX = reinterpret_cast<float*>(base);
+  float* dU = reinterpret_cast<float*>(base + bx);
+  double* dP = reinterpret_cast<double*>(base + po);
+  int32_t* dS = reinterpret_cast<int32_t*>(base + po + bp);
+  uint8_t* dM = reinterpret_cast<uint8_t*>(dS + 4);
+  hipStream_t s = ctx->stream;
+  std::memcpy(hbase, objpts, bx);
+  std::memcpy(hbase + bx, imgpts, bu);
+  VO_HIP_CHECK(hipMemcpyAsync(base, hbase, bx + bu, hipMemcpyHostToDevice, s));
+  const int32_t offs[2] = {0, n};
+  pnp_run(ctx, dX, dU, offs, 1, K, iterations, reproj_err, confidence, dP, dM, dS);
+  VO_HIP_CHECK(hipMemcpyAsync(hbase + po, dP, total - po, hipMemcpyDeviceToHost, s));
+  VO_HIP_CHECK(hipStreamSynchronize(s));
+  const double* pose = reinterpret_cast<const double*>(hbase + po);
+  const int32_t* status = reinterpret_cast<const int32_t*>(hbase + po + bp);
+  std::memcpy(mask_out, hbase + po + bp + 16, bm);
+  for (int k = 0; k < 3; ++k) {
+    rvec_out[k] = pose[k];
+    tvec_out[k] = pose[3 + k];
+  }
+  *success_out = status[0];
+}
+
+void pnp_last_split(vo_ctx* ctx, int* h1, int* tail_frames) {
+  PnpWorkspace& ws = ctx->pnp;
+  const int batch = (int)ws.offsets.size() - 1;
+  *h1 = ws.last_h1;
+  *tail_frames = 0;
+  if (batch <= 0 || ws.last_h1 >= ws.H) return;
+  std::vector<int32_t> need(batch);
+  VO_HIP_CHECK(hipMemcpyAsync(need.data(), ws.need.ptr, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, ctx->stream));
+  VO_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  for (int v : need) *tail_frames += v != 0;
+}
+
 }  // namespace vo

@@ -23,6 +23,7 @@
 //                         accepted keypoints appended with an atomic counter and put in
 //                         (image, octave, level, row, column) order on the host.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -758,6 +759,64 @@ int sift_layout(int h, int w, int n_layers, int64_t* out, int n) {
   const int m = std::min<int>(n, (int)v.size());
   for (int i = 0; i < m; ++i) out[i] = v[i];
   return (int)v.size();
+}
+
+void sift_detect_host(vo_ctx* ctx, const uint8_t* img, int h, int w, double contrast, double edge, double sigma,
+                      int n_layers, int capacity, float* kp_f, int32_t* kp_i, int32_t* count) {
+  SiftWorkspace& ws = ctx->sift;
+  const size_t nimg = (size_t)h * w;
+  const size_t cap = (size_t)std::max(capacity, 1);
+  ws.img.reserve(nimg);
+  ws.kp.reserve(cap * 64 + 64);
+  float* dF = ws.kp.as<float>();
+  int32_t* dI = reinterpret_cast<int32_t*>(dF + cap * 8);
+  int32_t* dC = dI + cap * 8;
+  hipStream_t s = ctx->stream;
+  VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, nimg, hipMemcpyHostToDevice, s));
+  sift_run(ctx, ws.img.as<uint8_t>(), 1, h, w, contrast, edge, sigma, n_layers, capacity, dF, dI, dC, nullptr, nullptr,
+           nullptr);
+  int32_t found = 0;
+  VO_HIP_CHECK(hipMemcpyAsync(&found, dC, 4, hipMemcpyDeviceToHost, s));
+  VO_HIP_CHECK(hipStreamSynchronize(s));
+  const int k = std::min(found, capacity);
+  *count = found;
+  if (k == 0) return;
+  std::vector<float> F((size_t)k * 8);
+  std::vector<int32_t> I((size_t)k * 8);
+  VO_HIP_CHECK(hipMemcpyAsync(F.data(), dF, F.size() * 4, hipMemcpyDeviceToHost, s));
+  VO_HIP_CHECK(hipMemcpyAsync(I.data(), dI, I.size() * 4, hipMemcpyDeviceToHost, s));
+  VO_HIP_CHECK(hipStreamSynchronize(s));
+  // (image, octave, candidate level, candidate row, candidate column): OpenCV's loop order
+  std::vector<int> ord(k);
+  for (int i = 0; i < k; ++i) ord[i] = i;
+  auto key = [&](int i) {
+    const int32_t* q = &I[(size_t)i * 8];
+    return std::array<int64_t, 6>{q[0], q[1] & 255, q[2], q[6], q[7], i};
+  };
+  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return key(a) < key(b); });
+  for (int i = 0; i < k; ++i) {
+    std::memcpy(kp_f + (size_t)i * 8, &F[(size_t)ord[i] * 8], 32);
+    std::memcpy(kp_i + (size_t)i * 8, &I[(size_t)ord[i] * 8], 32);
+  }
+}
+
+void sift_pyramid_host(vo_ctx* ctx, const uint8_t* img, int h, int w, double sigma, int n_layers, float* g_out,
+                       int64_t g_floats, float* d_out, int64_t d_floats) {
+  int64_t lay[3];
+  sift_layout(h, w, n_layers, lay, 3);
+  VO_REQUIRE(g_floats >= lay[1] && d_floats >= lay[2], VO_ERR_ARG,
+             "vo_sift_pyramid: outputs too small (%lld/%lld floats needed)", (long long)lay[1], (long long)lay[2]);
+  SiftWorkspace& ws = ctx->sift;
+  ws.img.reserve((size_t)h * w);
+  ws.kp.reserve(64);
+  hipStream_t s = ctx->stream;
+  VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, (size_t)h * w, hipMemcpyHostToDevice, s));
+  float *G = nullptr, *D = nullptr;
+  sift_run(ctx, ws.img.as<uint8_t>(), 1, h, w, 0.04, 10.0, sigma, n_layers, 0, nullptr, nullptr, ws.kp.as<int32_t>(), &G,
+           &D, nullptr);
+  VO_HIP_CHECK(hipMemcpyAsync(g_out, G, (size_t)lay[1] * 4, hipMemcpyDeviceToHost, s));
+  VO_HIP_CHECK(hipMemcpyAsync(d_out, D, (size_t)lay[2] * 4, hipMemcpyDeviceToHost, s));
+  VO_HIP_CHECK(hipStreamSynchronize(s));
 }
 
 }  // namespace vo

@@ -1027,9 +1027,7 @@ void sift_testing_select(vo_ctx* ctx, const float* okp, const int32_t* counts, i
 }
 
 // Orientation, filtering and descriptors of the candidates sift_run left in the workspace.
-int sift_max_capacity() { return kMaxCapImg; }
-
-void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double sigma, int nfeatures, int cap_img,
+static void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double sigma, int nfeatures, int cap_img,
                    const float* cand_f, const int32_t* cand_i, const int32_t* cand_count, int cand_cap,
                    const float* G, vo_sift_keypoint* d_kp, float* d_desc, int32_t* d_count) {
   VO_REQUIRE(batch >= 1 && batch <= kMaxBatch, VO_ERR_ARG, "sift: batch %d outside 1..%d", batch, kMaxBatch);
@@ -1101,6 +1099,64 @@ void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double si
   hipLaunchKernelGGL(sift_desc_kernel, dim3(std::max(1, ctx->num_cus * kDescWgPerCu)), dim3(kDescThreads), 0, st, da);
   VO_HIP_CHECK(hipGetLastError());
   ctx->prof.end(st);
+}
+
+// detectAndCompute of a device batch: detection into the workspace's candidate list, then
+// orientation / filtering / descriptors into the caller's buffers.
+void sift_detect_and_compute_run(vo_ctx* ctx, const uint8_t* d_imgs, int batch, int h, int w, int nfeatures,
+                                 double contrast, double edge, double sigma, int n_layers, int capacity,
+                                 vo_sift_keypoint* d_kps, float* d_desc, int32_t* d_counts) {
+  VO_REQUIRE(d_imgs && d_kps && d_desc && d_counts && batch >= 1 && capacity >= 1 && nfeatures >= 0, VO_ERR_ARG,
+             "sift detectAndCompute: bad arguments");
+  SiftWorkspace& ws = ctx->sift;
+  const int cand_cap = (int)std::min<int64_t>((int64_t)batch * capacity, 1 << 24);
+  ws.cand.reserve((size_t)cand_cap * 64 + 64);
+  float* cf = ws.cand.as<float>();
+  int32_t* ci = reinterpret_cast<int32_t*>(cf + (size_t)cand_cap * 8);
+  int32_t* cc = ci + (size_t)cand_cap * 8;
+  float* G = nullptr;
+  sift_run(ctx, d_imgs, batch, h, w, contrast, edge, sigma, n_layers, cand_cap, cf, ci, cc, &G, nullptr, nullptr);
+  sift_describe(ctx, batch, h, w, n_layers, sigma, nfeatures, capacity, cf, ci, cc, cand_cap, G, d_kps, d_desc,
+                d_counts);
+}
+
+void sift_detect_and_compute_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int nfeatures, double contrast,
+                                  double edge, double sigma, int n_layers, int capacity, vo_sift_keypoint* kps,
+                                  float* desc, int32_t* count, bool device_out, const char* fn) {
+  SiftWorkspace& ws = ctx->sift;
+  const size_t nimg = (size_t)h * w;
+  ws.img.reserve(nimg);
+  hipStream_t s = ctx->stream;
+  VO_HIP_CHECK(hipMemcpyAsync(ws.img.ptr, img, nimg, hipMemcpyHostToDevice, s));
+  // The working capacity (oriented keypoints before duplicate removal and retainBest)
+  // starts at the caller's -- for device outputs at 32768 at least, as the host wrapper's
+  // default buffers do: before retainBest the oriented keypoints outnumber the output many
+  // times --; an overflowing pass reports the capacity it needed (-n) and the next pass takes
+  // that (at least twice the last, at most the kernel limit: OpenCV has no cap); only the
+  // final keypoints must fit the caller's buffers.
+  int cap = std::min(device_out ? std::max(capacity, 1 << 15) : capacity, kMaxCapImg), n = -1;
+  vo_sift_keypoint* dK = nullptr;
+  float* dD = nullptr;
+  for (;;) {
+    ws.out.reserve((size_t)cap * (sizeof(vo_sift_keypoint) + 128 * sizeof(float)) + 64);
+    dK = ws.out.as<vo_sift_keypoint>();
+    dD = reinterpret_cast<float*>(dK + cap);
+    int32_t* dC = reinterpret_cast<int32_t*>(dD + (size_t)cap * 128);
+    sift_detect_and_compute_run(ctx, ws.img.as<uint8_t>(), 1, h, w, nfeatures, contrast, edge, sigma, n_layers, cap, dK,
+                                dD, dC);
+    VO_HIP_CHECK(hipMemcpyAsync(&n, dC, 4, hipMemcpyDeviceToHost, s));
+    VO_HIP_CHECK(hipStreamSynchronize(s));
+    if (n >= 0 || cap >= kMaxCapImg) break;
+    cap = (int)std::min<int64_t>(std::max<int64_t>(-(int64_t)n, 2ll * cap), kMaxCapImg);
+  }
+  VO_REQUIRE(n >= 0, VO_ERR_ARG, "%s: more than %d keypoints in one image", fn, cap);
+  VO_REQUIRE(n <= capacity, VO_ERR_ARG, "%s: %d keypoints exceed capacity=%d", fn, n, capacity);
+  *count = n;
+  if (n == 0) return;
+  const hipMemcpyKind kind = device_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  VO_HIP_CHECK(hipMemcpyAsync(kps, dK, (size_t)n * sizeof(vo_sift_keypoint), kind, s));
+  VO_HIP_CHECK(hipMemcpyAsync(desc, dD, (size_t)n * 128 * sizeof(float), kind, s));
+  VO_HIP_CHECK(hipStreamSynchronize(s));
 }
 
 }  // namespace vo

@@ -147,4 +147,24 @@ void tri_run(vo_ctx* ctx, const double* P1, const double* P2, const double* T_cw
   VO_HIP_CHECK(hipGetLastError());
 }
 
+void triangulate_host(vo_ctx* ctx, const double* P1, const double* P2, const double* T_cw2, const double* K,
+                      const float* pts1, const float* pts2, int n, double min_depth, double max_reproj_err,
+                      float* pts3d_out, uint8_t* mask_out) {
+  // staging: pts1 | pts2 | pts3d | mask
+  const size_t in = (size_t)n * 2 * sizeof(float), out3 = (size_t)n * 3 * sizeof(float);
+  ctx->tri.stage.reserve(2 * in + out3 + (size_t)n + 64);
+  char* base = ctx->tri.stage.as<char>();
+  float* d1 = reinterpret_cast<float*>(base);
+  float* d2 = reinterpret_cast<float*>(base + in);
+  float* d3 = reinterpret_cast<float*>(base + 2 * in);
+  uint8_t* dm = reinterpret_cast<uint8_t*>(base + 2 * in + out3);
+  hipStream_t st = ctx->stream;
+  VO_HIP_CHECK(hipMemcpyAsync(d1, pts1, in, hipMemcpyHostToDevice, st));
+  VO_HIP_CHECK(hipMemcpyAsync(d2, pts2, in, hipMemcpyHostToDevice, st));
+  tri_run(ctx, P1, P2, T_cw2, K, d1, d2, n, min_depth, max_reproj_err, d3, dm);
+  VO_HIP_CHECK(hipMemcpyAsync(pts3d_out, d3, out3, hipMemcpyDeviceToHost, st));
+  VO_HIP_CHECK(hipMemcpyAsync(mask_out, dm, (size_t)n, hipMemcpyDeviceToHost, st));
+  VO_HIP_CHECK(hipStreamSynchronize(st));
+}
+
 }  // namespace vo

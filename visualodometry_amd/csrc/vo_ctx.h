@@ -19,7 +19,6 @@ struct MatchWorkspace {
   DevBuf top2;      // int32 (n0, 2) + float (n0, 2)
   DevBuf pairs;     // int32 (n0, 2) compacted pairs + count
   DevBuf flag;      // uint32: == gen when this call's descriptors are not 0..255 integers
-  DevBuf tri;       // triangulation staging: pts1, pts2, pts3d, mask
   DevBuf hbf;       // float path: bf16 images of both sides (match_bf16.hip)
   DevBuf fnorm;     // float path: |b'|^2 per train row, |a| per query row
   DevBuf fpart;     // float path: top-2 of A per (split, row), the sweeps' own split
@@ -47,6 +46,11 @@ struct MatchQueryCache {
   int n0 = -1, dim = -1;
   bool device_src = false;
   bool valid = false;
+};
+
+// Triangulation workspace (tri.hip).
+struct TriWorkspace {
+  DevBuf stage;  // host-call staging: pts1, pts2, pts3d, mask
 };
 
 // PnP-RANSAC workspace (pnp.hip): RANSAC subsets cached per frame layout.
@@ -167,6 +171,7 @@ struct vo_ctx {
   int num_cus = 0;
   vo::MatchWorkspace match;
   vo::MatchQueryCache match_q;
+  vo::TriWorkspace tri;
   vo::PnpWorkspace pnp;
   vo::EssWorkspace ess;
   vo::SiftWorkspace sift;
@@ -189,39 +194,51 @@ struct vo_ctx {
 };
 
 namespace vo {
-// Matcher entry points (match.hip).
+// Matcher entry points (match.hip).  match_run, match_mutual_batch: device arrays, asynchronous.
+// match_host: host arrays (device descriptors with device_src), synchronous.
 void match_run(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0,
                int n1, int dim, double ratio, int32_t* d_best, int32_t* d_idx2,
                float* d_dist2, const MatchQueryCache* qc = nullptr, int32_t* d_rev = nullptr);
-void mutual_filter(vo_ctx* ctx, int32_t* d_best, const int32_t* d_rev, int batch, int n0, int n1);
-void match_pack_query(vo_ctx* ctx, const float* d_des0, int n0, int dim, MatchQueryCache& qc);
+void match_mutual_batch(vo_ctx* ctx, const float* d_des0, const float* d_des1, int batch, int n0, int n1, int dim,
+                        double ratio, int32_t* d_best);
+void match_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim,
+                double ratio, int32_t* pairs, int32_t* count, int32_t* idx2, float* dist2, uint64_t q_tag = 0,
+                bool device_src = false, bool mutual = false);
 void compact_pairs(vo_ctx* ctx, const int32_t* d_best, int n0, int32_t* d_pairs,
                    int32_t* d_count);
-// Projection-gated and segment-gated matcher (match_gate.hip): device arrays in, best (n0) and dist (n0) out.
-struct GateArgs {
-  const float* des0;    // (n0, dim)
-  const float* des1;    // (n1, dim)
-  const float* pred;    // (n0, 2); with segment (n0, 4): ax, ay, bx, by
+// Projection-gated and segment-gated matcher (match_gate.hip): host arrays (device train rows and
+// keypoints with dev), synchronous; the arguments are checked by the caller.
+struct GateHostArgs {
+  const float* query;   // (n0, qcols) the gate's per-query array
+  int qcols;            // 2: predicted position (circular gate); 4: segment a, b (capsule gate)
   const float* radius;  // (n0) or null: radius0
   const float* kp1;     // (n1, 2)
   float radius0;
-  int n0, n1, dim, width, height;
+  int width, height;
   double ratio, max_dist;
   bool unique;
-  bool segment;         // the capsule gate of vo_match_segment around pred's segments
-  int32_t* best;        // (n0) kept train row or -1
-  float* dist;          // (n0) dist1 of the kept pair (unspecified where best is -1)
+  bool dev;             // des1 and kp1 are device arrays
 };
-size_t gate_scratch_bytes(int n1, int width, int height);
-void gate_run(vo_ctx* ctx, const GateArgs& a, void* scratch);
-// Triangulation entry point (tri.hip): host matrices, device points.
+void match_gate_host(vo_ctx* ctx, const float* des0, int n0, const float* des1, int n1, int dim, const GateHostArgs& h,
+                     int32_t* out_pairs, float* out_dist, int32_t* out_count);
+// Triangulation (tri.hip).  tri_run: host matrices, device points, asynchronous.  triangulate_host:
+// host arrays, synchronous; the arguments are checked by the caller.
 void tri_run(vo_ctx* ctx, const double* P1, const double* P2, const double* T_cw2, const double* K,
              const float* d_pts1, const float* d_pts2, int n, double min_depth, double max_reproj_err,
              float* d_pts3d, uint8_t* d_mask);
-// PnP-RANSAC entry point (pnp.hip): device points, host offsets and K.
+void triangulate_host(vo_ctx* ctx, const double* P1, const double* P2, const double* T_cw2, const double* K,
+                      const float* pts1, const float* pts2, int n, double min_depth, double max_reproj_err,
+                      float* pts3d_out, uint8_t* mask_out);
+// PnP-RANSAC (pnp.hip).  pnp_run: device points, host offsets and K, asynchronous.  pnp_ransac_host:
+// host arrays, synchronous; the arguments are checked by the caller.
 void pnp_run(vo_ctx* ctx, const float* d_X, const float* d_uv, const int32_t* offsets, int batch,
              const double* K, int iterations, double reproj_err, double confidence, double* d_pose,
              uint8_t* d_mask, int32_t* d_status);
+void pnp_ransac_host(vo_ctx* ctx, const float* objpts, const float* imgpts, int n, const double* K, int iterations,
+                     double reproj_err, double confidence, double* rvec_out, double* tvec_out, uint8_t* mask_out,
+                     int32_t* success_out);
+// The last pnp_run's split (test entry vo_pnp_testing_last_split): reads the frames' need flags back.
+void pnp_last_split(vo_ctx* ctx, int* h1, int* tail_frames);
 void pnp_subsets(int count, int iters, int32_t* out);
 // Essential-matrix RANSAC and recoverPose (essential.hip): host arrays, synchronous.
 void essential_ransac_host(vo_ctx* ctx, const float* pts1, const float* pts2, int n, const double* K, int max_iters,
@@ -244,16 +261,27 @@ void corner_response_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int blo
 void corner_select_host(vo_ctx* ctx, const int32_t* xy, const float* resp, int n, const float* keep, int n_keep,
                         float min_distance, int max_corners, int32_t* out_idx, int32_t* n_out);
 void corner_stats(vo_ctx* ctx, int32_t out[4]);
-// SIFT detection (sift.hip): device images, device keypoint outputs (unsorted).
+// SIFT detection (sift.hip).  sift_run: device images, device keypoint outputs (unsorted),
+// asynchronous.  sift_detect_host (keypoints in OpenCV's order) and sift_pyramid_host: host
+// arrays, synchronous; the arguments are checked by the caller.
 void sift_run(vo_ctx* ctx, const uint8_t* d_img, int batch, int h, int w, double contrast, double edge,
               double sigma, int n_layers, int capacity, float* d_kpf, int32_t* d_kpi, int32_t* d_count,
               float** g_out, float** d_out, int64_t* layout);
+void sift_detect_host(vo_ctx* ctx, const uint8_t* img, int h, int w, double contrast, double edge, double sigma,
+                      int n_layers, int capacity, float* kp_f, int32_t* kp_i, int32_t* count);
+void sift_pyramid_host(vo_ctx* ctx, const uint8_t* img, int h, int w, double sigma, int n_layers, float* g_out,
+                       int64_t g_floats, float* d_out, int64_t d_floats);
 int sift_layout(int h, int w, int n_layers, int64_t* out, int n);
-// SIFT orientation, filtering and descriptors (sift_desc.hip) of sift_run's candidates.
-int sift_max_capacity();  // largest per-image keypoint capacity of sift_describe
-void sift_describe(vo_ctx* ctx, int batch, int h, int w, int n_layers, double sigma, int nfeatures, int cap_img,
-                   const float* cand_f, const int32_t* cand_i, const int32_t* cand_count, int cand_cap,
-                   const float* G, vo_sift_keypoint* d_kp, float* d_desc, int32_t* d_count);
+// SIFT detectAndCompute (sift_desc.hip): sift_run's candidates, then orientation, filtering and
+// descriptors.  _run: a device batch into the caller's device buffers, asynchronous.  _host: a
+// host image, synchronous, the results copied to host arrays or (device_out) to the caller's
+// device buffers; fn names the entry in the messages; the arguments are checked by the caller.
+void sift_detect_and_compute_run(vo_ctx* ctx, const uint8_t* d_imgs, int batch, int h, int w, int nfeatures,
+                                 double contrast, double edge, double sigma, int n_layers, int capacity,
+                                 vo_sift_keypoint* d_kps, float* d_desc, int32_t* d_counts);
+void sift_detect_and_compute_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int nfeatures, double contrast,
+                                  double edge, double sigma, int n_layers, int capacity, vo_sift_keypoint* kps,
+                                  float* desc, int32_t* count, bool device_out, const char* fn);
 // sift_describe's selection stage alone on host records (test entry vo_sift_testing_select).
 void sift_testing_select(vo_ctx* ctx, const float* okp, const int32_t* counts, int batch, int cap_img, int nfeatures,
                          uint32_t* sel, int32_t* sel_count);
