@@ -905,6 +905,71 @@ int vo_corner_select(vo_ctx* ctx, const int32_t* xy, const float* resp, int n, c
  * rounds that had something to decide, corners accepted, grid cell side]. */
 int vo_corner_stats(vo_ctx* ctx, int32_t out[4]);
 
+/* ---- BRIEF (steered binary descriptor) and the Hamming matcher ------------ */
+/* A 256-bit descriptor of the 31 x 31 patch around a point of an h x w uint8 image: ORB's structure
+ * (intensity-centroid direction, steered BRIEF over box sums), not its bits.  Build-defined; the
+ * contract is restated in tests/brief_ref.py.  Every quantity is an integer, so results do not
+ * depend on how the device computes them.
+ *   Direction tables C[32], S[32] (int32): for k = 0..7, C[k] = rint(16384 cos(2 pi k / 32)),
+ *   S[k] = rint(16384 sin(2 pi k / 32)); for k = 8..31, C[k] = -S[k-8], S[k] = C[k-8] (a quarter turn
+ *   is exact).
+ *   Base pattern, 256 tests (px, py, qx, qy): a 64-bit LCG s <- s * 6364136223846793005 +
+ *   1442695040888963407 (mod 2^64) from s = 0x5EED; a draw is (s >> 33) % 9 - 4; a coordinate is the
+ *   sum of three consecutive draws, drawn in the order px, py, qx, qy; a test is drawn again if
+ *   px^2 + py^2 > 144, qx^2 + qy^2 > 144, p == q, or the 4-tuple was already taken.
+ *   Rotated pattern P[32][256][4] (int8): rx = (x C[k] - y S[k] + 8192) >> 14,
+ *   ry = (x S[k] + y C[k] + 8192) >> 14, the shift arithmetic (a floor).  Every |coordinate| <= 12;
+ *   P[k+8] is (-y, x) of P[k].  (csrc/brief_pattern.h, written by tools/make_brief_pattern.py.)
+ *   Per point (x, y), float32:
+ *   1. Status 1 (zero descriptor, bin 0) if a coordinate is not finite or |coordinate| >= 2^24;
+ *      else cx = (int)rintf(x), cy = (int)rintf(y) (half to even); status 1 if cx is outside
+ *      [0, w-1] or cy outside [0, h-1]; else status 0.
+ *   2. Patch: I(reflect(cx+dx, w), reflect(cy+dy, h)), dx, dy in [-15, 15], the reflection of the
+ *      corner detector above (total for any extent): a corner at the border is described too.
+ *   3. Moments (int32): m10 = sum dx I, m01 = sum dy I over dx^2 + dy^2 <= 225 (709 pixels).
+ *   4. Bin: the k maximising (int64)m10 C[k] + (int64)m01 S[k], ties to the lowest k.
+ *   5. Box sums: B(u, v) = sum of the 5 x 5 patch pixels centred (u, v), |u|, |v| <= 13.
+ *   6. Bit t = B(P[k][t].p) < B(P[k][t].q), strictly, stored in word t / 32 at bit t % 32 of eight
+ *      uint32 words.
+ * pts (n, 2), des_out (n, 8), bin_out (n, optional) and status_out (n, optional) are host arrays.
+ * tag is vo_good_features' tag: level 0 of a cached KLT pyramid entry with that tag, h and w is read
+ * instead of img (which may then be NULL); the cache is only read; results never depend on it.
+ * n == 0: VO_OK, no device touched.  flags must be 0.
+ *   VO_ERR_ARG (before the context or a device is touched): des_out NULL, pts NULL with n > 0, a
+ *   NULL image with tag 0, h < 1, w < 1, h*w > 2^30, n < 0, nonzero flags.
+ * The kernels are not in the profiler's id table (tools/brief_timing.py times the calls). */
+int vo_brief_describe(vo_ctx* ctx, const uint8_t* img, uint64_t tag, int h, int w, const float* pts, int n, int flags,
+                      uint32_t* des_out, int32_t* bin_out, uint8_t* status_out);
+/* The tables: out = P as int8 [32][256][4], dir_out = C[32] then S[32].  Needs no context. */
+int vo_brief_pattern(int8_t out[32 * 256 * 4], int32_t dir_out[64]);
+
+/* Brute-force Hamming matching of binary rows: des0 (n0, words), des1 (n1, words) uint32, words in
+ * 1..16; d(i, j) = sum over the words of popcount(a_w ^ b_w).
+ *   Top-2 per query under keys (d, j): equal distances keep the lower j.  knn_idx (n0, 2) and
+ *   knn_dist (n0, 2) (both optional) receive them, -1 and INT32_MAX where no neighbour exists.
+ *   A query with fewer than two neighbours emits no pair (as vo_match_knn2_ratio).  (i, j1) is kept
+ *   iff (max_dist == 0 or d1 <= max_dist) and (double)d1 < ratio * (double)d2.  With
+ *   VO_MATCH_HAMMING_MUTUAL a kept pair survives iff i has the smallest key (d(i', j1), i') over all
+ *   query rows i'.  Pairs come out in ascending query order: out_pairs (capacity 2 * n0 int32),
+ *   out_dist (n0, optional) their distances, *out_count their number.
+ *   VO_MATCH_DEVICE_PTRS: des0 and des1 are device pointers of this process's HIP runtime on the
+ *   context's GPU (as in vo_match_mutual); every output is a host array.
+ *   VO_ERR_ARG (before any launch; the options' and the shapes' checks need no device): opt,
+ *   out_pairs or out_count NULL, a NULL array with a nonzero size, negative sizes, words outside
+ *   1..16, a ratio that is not finite or negative, a negative max_dist, unknown flag bits, nonzero
+ *   reserved.
+ * Results do not depend on how the device splits the work: every distance is an integer. */
+#define VO_MATCH_HAMMING_MUTUAL 4
+typedef struct {
+  double ratio;      /* finite, >= 0 */
+  int32_t max_dist;  /* >= 0; 0: no limit */
+  int32_t flags;     /* VO_MATCH_DEVICE_PTRS | VO_MATCH_HAMMING_MUTUAL */
+  int32_t reserved;  /* 0 */
+} vo_match_hamming_options;
+int vo_match_hamming(vo_ctx* ctx, const uint32_t* des0, int n0, const uint32_t* des1, int n1, int words,
+                     const vo_match_hamming_options* opt, int32_t* out_pairs, int32_t* out_dist, int32_t* out_count,
+                     int32_t* knn_idx, int32_t* knn_dist);
+
 /* ---- multi-GPU (landmark sharding + RCCL all-reduce) --------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and shared by the caller. */
 int vo_comm_unique_id(char out[128]);

@@ -28,6 +28,7 @@ VO_ERR_STATE = -6
 VO_ERR_NODEV = -7
 VO_MATCH_DEVICE_PTRS = 1  # vo_match_mutual / vo_match_gated / vo_match_segment flags
 VO_MATCH_GATE_UNIQUE = 2  # vo_match_gated / vo_match_segment: one-to-one output
+VO_MATCH_HAMMING_MUTUAL = 4  # vo_match_hamming: cross check
 STATUS_NAMES = {
     VO_OK: "ok", VO_ERR_ARG: "bad argument", VO_ERR_HIP: "HIP error",
     VO_ERR_NOT_SPD: "not positive definite", VO_ERR_RCCL: "RCCL error",
@@ -94,6 +95,11 @@ class CornerOptionsC(C.Structure):
     """``vo_corner_options``: limit, block, quality and distance of ``vo_good_features``."""
     _fields_ = [("max_corners", C.c_int32), ("block_radius", C.c_int32), ("quality", C.c_float),
                 ("min_distance", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MatchHammingOptionsC(C.Structure):
+    """``vo_match_hamming_options``: the keep rule and the flags of ``vo_match_hamming``."""
+    _fields_ = [("ratio", C.c_double), ("max_dist", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 VO_KLT_GUESS = 1  # vo_klt_track flags: pts1 holds the initial guess on entry
@@ -198,6 +204,11 @@ SIGNATURES = {
     "vo_corner_response": (_I, [_P, C.c_void_p, _I, _I, _I, C.c_void_p]),
     "vo_corner_select": (_I, [_P, C.c_void_p, C.c_void_p, _I, C.c_void_p, _I, C.c_float, _I, C.c_void_p, _PI32]),
     "vo_corner_stats": (_I, [_P, _PI32]),
+    "vo_brief_describe": (_I, [_P, C.c_void_p, C.c_uint64, _I, _I, C.c_void_p, _I, _I, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "vo_brief_pattern": (_I, [C.c_void_p, C.c_void_p]),
+    "vo_match_hamming": (_I, [_P, C.c_void_p, _I, C.c_void_p, _I, _I, C.POINTER(MatchHammingOptionsC), C.c_void_p,
+                              C.c_void_p, _PI32, C.c_void_p, C.c_void_p]),
     "vo_sift_detect": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _D, _D, _D, _I, _I, _PF, _PI32, _PI32]),
     "vo_sift_detect_batch_async": (_I, [_P, _P, _I, _I, _I, _D, _D, _D, _I, _I, _P, _P, _P]),
     "vo_sift_pyramid": (_I, [_P, C.POINTER(C.c_uint8), _I, _I, _D, _I, _PF, C.c_int64, _PF, C.c_int64]),

@@ -476,6 +476,65 @@ int vo_corner_stats(vo_ctx* ctx, int32_t out[4]) {
   });
 }
 
+int vo_brief_describe(vo_ctx* ctx, const uint8_t* img, uint64_t tag, int h, int w, const float* pts, int n, int flags,
+                      uint32_t* des_out, int32_t* bin_out, uint8_t* status_out) {
+  return guarded([&] {
+    // the arguments' own checks first: they need no device (nor a context)
+    VO_REQUIRE(des_out, VO_ERR_ARG, "vo_brief_describe: null des_out");
+    VO_REQUIRE(n >= 0 && h >= 1 && w >= 1, VO_ERR_ARG, "vo_brief_describe: bad shape n=%d h=%d w=%d", n, h, w);
+    VO_REQUIRE((int64_t)h * w <= (int64_t)1 << 30, VO_ERR_ARG,
+               "vo_brief_describe: bad shape, %d x %d is above 2^30 pixels", h, w);
+    VO_REQUIRE(n == 0 || pts, VO_ERR_ARG, "vo_brief_describe: null pts with n > 0");
+    VO_REQUIRE(img || tag, VO_ERR_ARG, "vo_brief_describe: null image with tag 0");
+    VO_REQUIRE(flags == 0, VO_ERR_ARG, "vo_brief_describe: unknown flags 0x%x", flags);
+    if (n == 0) return;
+    vo::bind(ctx);
+    vo::brief_describe_host(ctx, img, tag, h, w, pts, n, des_out, bin_out, status_out);
+  });
+}
+
+int vo_brief_pattern(int8_t out[32 * 256 * 4], int32_t dir_out[64]) {
+  return guarded([&] {
+    VO_REQUIRE(out && dir_out, VO_ERR_ARG, "vo_brief_pattern: null outputs");
+    vo::brief_pattern(out, dir_out);
+  });
+}
+
+int vo_match_hamming(vo_ctx* ctx, const uint32_t* des0, int n0, const uint32_t* des1, int n1, int words,
+                     const vo_match_hamming_options* opt, int32_t* out_pairs, int32_t* out_dist, int32_t* out_count,
+                     int32_t* knn_idx, int32_t* knn_dist) {
+  return guarded([&] {
+    // the arguments' own checks first: they need no device (nor a context)
+    VO_REQUIRE(opt && out_pairs && out_count, VO_ERR_ARG, "vo_match_hamming: null options or outputs");
+    VO_REQUIRE(n0 >= 0 && n1 >= 0 && words >= 1 && words <= 16, VO_ERR_ARG,
+               "vo_match_hamming: bad shape n0=%d n1=%d words=%d", n0, n1, words);
+    VO_REQUIRE((opt->flags & ~(VO_MATCH_DEVICE_PTRS | VO_MATCH_HAMMING_MUTUAL)) == 0, VO_ERR_ARG,
+               "vo_match_hamming: unknown flags 0x%x", opt->flags);
+    VO_REQUIRE(opt->reserved == 0, VO_ERR_ARG, "vo_match_hamming: reserved must be 0");
+    VO_REQUIRE(std::isfinite(opt->ratio) && opt->ratio >= 0.0 && opt->max_dist >= 0, VO_ERR_ARG,
+               "vo_match_hamming: ratio must be finite and >= 0, max_dist >= 0");
+    VO_REQUIRE((n0 == 0 || des0) && (n1 == 0 || des1), VO_ERR_ARG, "vo_match_hamming: null array with a nonzero size");
+    *out_count = 0;
+    if (n0 == 0) return;
+    if (n1 == 0) {  // no neighbour exists
+      for (size_t k = 0; k < 2 * (size_t)n0; ++k) {
+        if (knn_idx) knn_idx[k] = -1;
+        if (knn_dist) knn_dist[k] = INT32_MAX;
+      }
+      return;
+    }
+    vo::bind(ctx);
+    const bool dev = (opt->flags & VO_MATCH_DEVICE_PTRS) != 0;
+    if (dev) {  // as vo_match_mutual: refused before any launch
+      vo::check_device_range(ctx, des0, (size_t)n0 * words * 4, "des0");
+      vo::check_device_range(ctx, des1, (size_t)n1 * words * 4, "des1");
+    }
+    vo::match_hamming_host(ctx, des0, n0, des1, n1, words, opt->ratio, opt->max_dist,
+                           (opt->flags & VO_MATCH_HAMMING_MUTUAL) != 0, dev, out_pairs, out_dist, out_count, knn_idx,
+                           knn_dist);
+  });
+}
+
 int vo_sift_detect(vo_ctx* ctx, const uint8_t* img, int h, int w, double contrast, double edge, double sigma,
                    int n_layers, int capacity, float* kp_f, int32_t* kp_i, int32_t* count) {
   return guarded([&] {

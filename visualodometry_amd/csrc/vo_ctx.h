@@ -138,6 +138,22 @@ struct CornerWorkspace {
   int32_t stats[4] = {0, 0, 0, 0};  // the last call's candidates, rounds, accepted, cell side
 };
 
+// Steered BRIEF workspace (brief.hip).
+struct BriefWorkspace {
+  DevBuf img;  // host-call staging: an untagged (or uncached) image
+  DevBuf pts;  // host-call staging: the points (n, 2)
+  DevBuf out;  // descriptors (n, 8), bins (n), status (n)
+};
+
+// Hamming matcher workspace (match_hamming.hip).
+struct HammingWorkspace {
+  DevBuf des;      // host-call staging: des0 then des1
+  DevBuf partial;  // uint64 keys: (slices, n0, 2) forward, then (slices, n1) reverse
+  DevBuf top2;     // int32 (n0, 2) indices, (n0, 2) distances
+  DevBuf best;     // int32 (n0): the kept train row or -1
+  DevBuf pairs;    // int32 (n0, 2) compacted pairs + count
+};
+
 class BAEngine;   // ba_engine.hip
 struct Comm;      // ba_comm.h (RCCL communicator or loopback group)
 
@@ -177,6 +193,8 @@ struct vo_ctx {
   vo::SiftWorkspace sift;
   vo::KltWorkspace klt;
   vo::CornerWorkspace corners;
+  vo::BriefWorkspace brief;
+  vo::HammingWorkspace hamming;
   vo::Profiler prof;
   std::unique_ptr<vo::BAEngine> ba;
   std::unique_ptr<vo::Comm> comm;
@@ -261,6 +279,15 @@ void corner_response_host(vo_ctx* ctx, const uint8_t* img, int h, int w, int blo
 void corner_select_host(vo_ctx* ctx, const int32_t* xy, const float* resp, int n, const float* keep, int n_keep,
                         float min_distance, int max_corners, int32_t* out_idx, int32_t* n_out);
 void corner_stats(vo_ctx* ctx, int32_t out[4]);
+// Steered BRIEF (brief.hip): host arrays, synchronous; the arguments are checked by the caller.
+void brief_describe_host(vo_ctx* ctx, const uint8_t* img, uint64_t tag, int h, int w, const float* pts, int n,
+                         uint32_t* des_out, int32_t* bin_out, uint8_t* status_out);
+void brief_pattern(int8_t* out, int32_t* dir_out);
+// Hamming matcher (match_hamming.hip): host outputs, host or (dev) device rows, synchronous; the
+// arguments are checked by the caller, n0 >= 1.
+void match_hamming_host(vo_ctx* ctx, const uint32_t* des0, int n0, const uint32_t* des1, int n1, int words, double ratio,
+                        int max_dist, bool mutual, bool dev, int32_t* out_pairs, int32_t* out_dist, int32_t* out_count,
+                        int32_t* knn_idx, int32_t* knn_dist);
 // SIFT detection (sift.hip).  sift_run: device images, device keypoint outputs (unsorted),
 // asynchronous.  sift_detect_host (keypoints in OpenCV's order) and sift_pyramid_host: host
 // arrays, synchronous; the arguments are checked by the caller.

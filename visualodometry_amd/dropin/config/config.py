@@ -110,11 +110,19 @@ class VOConfig:
     klt_min_distance: float = 8.0  # a replenishing detection keeps this distance from every tracked keypoint
     # replenish a new keyframe with Shi-Tomasi corners (visualodometry_amd.corners.good_features, which reads the
     # keyframe's cached pyramid and keeps away from the tracked points on the device) instead of SIFT detections.
-    # The corners carry no descriptor: they are tracked, never matched, so the switch excludes map_reobserve and
-    # map_epipolar_search.  Untuned starting values; no accuracy claimed.
+    # The corners carry no SIFT descriptor: the searches that read descriptors of keyframe rows cannot use them, so the
+    # switch excludes map_reobserve and map_epipolar_search.  Untuned starting values; no accuracy claimed.
     klt_corner_replenish: bool = False
     klt_corner_quality: float = 0.01  # a corner's response is above this fraction of the strongest one's
     klt_corner_block: int = 3  # block of the gradient sums: 3, 5 or 7
+    # give the corners a steered BRIEF descriptor (visualodometry_amd.brief.describe) so that a frame that falls back
+    # to detection can find the keyframe's corner rows again: such a frame also receives corners, and match_frames adds
+    # the Hamming matches (visualodometry_amd.matcher.match_hamming, cross-checked) between the two sets of corner rows
+    # to the SIFT pairs.  Read only under klt_corner_replenish; without it the switch does nothing.  The exclusion of
+    # map_reobserve and map_epipolar_search stays.  Untuned starting values; no accuracy claimed.
+    klt_corner_describe: bool = False
+    klt_brief_ratio: float = 0.8  # ratio test between the two nearest corner rows (untuned starting value)
+    klt_brief_max_dist: int = 64  # of 256 bits: the largest distance of a kept pair (untuned starting value)
 
 
 # dataset -> (overrides always applied, overrides applied when extractor is SIFT)
@@ -148,8 +156,9 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
     ``VO_AMD_EXTRACTOR=sift`` (as ``extractor_type``), ``VO_AMD_BA=1``
     (``ba_enabled``), ``VO_AMD_SP_BF=1`` (``superpoint_bf_match``), ``VO_AMD_INIT=1``
     (``init_on_gpu``), ``VO_AMD_REOBSERVE=1`` (``map_reobserve``), ``VO_AMD_EPIPOLAR=1``
-    (``map_epipolar_search``), ``VO_AMD_KLT=1`` (``klt_tracking``) and ``VO_AMD_KLT_CORNERS=1``
-    (``klt_corner_replenish``).  Unset, the result equals the reference's.
+    (``map_epipolar_search``), ``VO_AMD_KLT=1`` (``klt_tracking``), ``VO_AMD_KLT_CORNERS=1``
+    (``klt_corner_replenish``) and ``VO_AMD_KLT_BRIEF=1`` (``klt_corner_describe``).  Unset, the result
+    equals the reference's.
     """
     cfg = VOConfig()
     if extractor_type is None:
@@ -168,6 +177,8 @@ def get_config(dataset: str, extractor_type: str | None = None) -> VOConfig:
         cfg.klt_tracking = True
     if os.environ.get("VO_AMD_KLT_CORNERS", "0") not in ("", "0"):
         cfg.klt_corner_replenish = True
+    if os.environ.get("VO_AMD_KLT_BRIEF", "0") not in ("", "0"):
+        cfg.klt_corner_describe = True
     if extractor_type is not None:
         cfg.extractor_type = extractor_type
     base, sift = _DATASET_OVERRIDES.get(dataset, ({}, {}))

@@ -37,6 +37,10 @@ are the caller's environment):
   With ``cfg.klt_corner_replenish`` (off by default) the replenishment takes Shi-Tomasi corners
   (:func:`visualodometry_amd.corners.good_features`) instead of SIFT detections; their rows have no
   descriptor (a per-row flag says so) and a detected frame is matched against the others only.
+  With ``cfg.klt_corner_describe`` on top (off by default) the corners get steered BRIEF rows
+  (:func:`visualodometry_amd.brief.describe`), a frame that falls back to detection receives
+  described corners too, and ``match_frames`` adds the cross-checked Hamming matches between the
+  two sets of corner rows (:func:`visualodometry_amd.matcher.match_hamming`) to the SIFT pairs.
 
 The reference keeps only the current keyframe's observation of a freshly
 triangulated point (``vo.py:277-284``); the window also records the previous
@@ -437,6 +441,7 @@ def epipolar_search(vo, prev, curr_feats, curr_ids, ref_indices, curr_indices):
 _KLT_IMAGE, _KLT_TAG, _KLT_SRC, _KLT_SRC_IDX = "_vo_amd_klt_image", "_vo_amd_klt_tag", "_vo_amd_klt_src", \
     "_vo_amd_klt_src_idx"
 _KLT_HAS_DESC = "_vo_amd_klt_has_desc"  # cfg.klt_corner_replenish: (N,) bool, which rows carry a real descriptor
+_KLT_BRIEF = "_vo_amd_klt_brief"  # cfg.klt_corner_describe: (N, 8) uint32 BRIEF rows (zeros for rows with a descriptor)
 _klt_tags = itertools.count(1 << 40)  # pyramid-cache tags of the frames seen (one per image, never reused)
 
 
@@ -454,9 +459,14 @@ class KltTracker:
         self.min_distance = float(getattr(config, "klt_min_distance", 8.0))
         self.max_rows = int(getattr(config, "sift_n_features", 0) or 0)
         self.corners = bool(getattr(config, "klt_corner_replenish", False))
+        self.describe = False
         if self.corners:  # (off: neither setting is read)
             self.corner_quality = float(getattr(config, "klt_corner_quality", 0.01))
             self.corner_block = int(getattr(config, "klt_corner_block", 3))
+            self.describe = bool(getattr(config, "klt_corner_describe", False))
+            if self.describe:  # (off: neither setting is read)
+                self.brief_ratio = float(getattr(config, "klt_brief_ratio", 0.8))
+                self.brief_max_dist = int(getattr(config, "klt_brief_max_dist", 64))
             for other in ("map_reobserve", "map_epipolar_search"):
                 if getattr(config, other, False):
                     raise ValueError(f"klt_corner_replenish cannot be combined with {other}: that search reads "
@@ -517,14 +527,14 @@ def klt_process_image(st: KltTracker, img, detect):
         st.alive = np.arange(len(st.last), dtype=np.int64)
         st.kp0 = st.last.copy()
     if st.alive.size < st.min_tracks:
-        return detected()
+        return klt_describe_fallback(st, detected(), img, tag) if st.describe else detected()
     p1, status, _ = klt.track(src[_KLT_IMAGE], img, st.kp0[st.alive], guess=st.last, win_radius=st.win_radius,
                               levels=st.levels, fb_thresh=st.fb_thresh if st.fb_thresh > 0 else None,
                               tags=(src[_KLT_TAG], tag))
     ok = status == 0
     st.alive, st.last = st.alive[ok], np.ascontiguousarray(p1[ok])
     if st.alive.size < st.min_tracks:
-        return detected()
+        return klt_describe_fallback(st, detected(), img, tag) if st.describe else detected()
     feats = {
         "keypoints": _batched(_like(st.last, kp_ref), kp_ref),
         "descriptors": _batched(_rows(_descriptors(src), st.alive), src["descriptors"]),
@@ -534,6 +544,48 @@ def klt_process_image(st: KltTracker, img, detect):
         feats["image_size"] = src["image_size"]
     if _KLT_HAS_DESC in src:  # cfg.klt_corner_replenish: the flag follows its descriptor row
         feats[_KLT_HAS_DESC] = np.asarray(src[_KLT_HAS_DESC], bool)[st.alive]
+    if _KLT_BRIEF in src:  # cfg.klt_corner_describe: so does the BRIEF row
+        feats[_KLT_BRIEF] = np.asarray(src[_KLT_BRIEF], np.uint32)[st.alive]
+    return feats
+
+
+def _append_rows(old, extra):
+    """``extra`` appended to the rows of ``old`` (numpy or tensor, (N, D) or (1, N, D)), as ``old``'s kind."""
+    rows = old[0] if getattr(old, "ndim", 2) == 3 else old
+    if hasattr(rows, "detach"):
+        import torch
+
+        out = torch.cat([rows, torch.as_tensor(extra, dtype=rows.dtype, device=rows.device)])
+    else:
+        out = np.concatenate([rows, np.asarray(extra, rows.dtype)])
+    return _batched(out, old)
+
+
+def klt_describe_fallback(st: KltTracker, feats, img, tag):
+    """A frame that fell back to detection under ``cfg.klt_corner_describe``: Shi-Tomasi corners of
+    its image, at least ``klt_min_distance`` from its detections and from each other, as many as
+    ``sift_n_features`` rows leave room for, appended with a zero descriptor, a false flag under
+    ``_KLT_HAS_DESC`` and their BRIEF rows under ``_KLT_BRIEF``: what the keyframe's corner rows
+    are matched against (:func:`klt_descriptor_rows`)."""
+    from .. import brief, corners
+
+    if not isinstance(feats, dict):
+        return feats
+    kept = np.ascontiguousarray(_keypoints(feats), np.float32).reshape(-1, 2)
+    n = len(kept)
+    room = max(st.max_rows - n, 0) if st.max_rows > 0 else None
+    if room == 0:
+        add = np.zeros((0, 2), np.float32)
+    else:
+        add, _ = corners.good_features(img, room, quality=st.corner_quality, min_distance=st.min_distance,
+                                       block_size=st.corner_block, keep=kept, tag=tag)
+    rows = brief.describe(img, add, tag=tag)[0] if len(add) else np.zeros((0, brief.WORDS), np.uint32)
+    des = feats["descriptors"]
+    width = (des[0] if getattr(des, "ndim", 2) == 3 else des).shape[1]
+    feats["keypoints"] = _append_rows(feats["keypoints"], add)
+    feats["descriptors"] = _append_rows(des, np.zeros((len(add), width), np.float32))
+    feats[_KLT_HAS_DESC] = np.concatenate([np.ones(n, bool), np.zeros(len(add), bool)])
+    feats[_KLT_BRIEF] = np.concatenate([np.zeros((n, brief.WORDS), np.uint32), rows])
     return feats
 
 
@@ -616,7 +668,10 @@ def klt_replenish_corners(vo, st: KltTracker, feats: dict) -> int:
     """:func:`klt_replenish` under ``cfg.klt_corner_replenish``: Shi-Tomasi corners of the keyframe's
     image (its cached pyramid's level 0), at least ``klt_min_distance`` from every keypoint it has
     and from each other, as many as ``sift_n_features`` rows leave room for, strongest first.  Their
-    rows get id -1, a zero descriptor and a false flag under ``_KLT_HAS_DESC``."""
+    rows get id -1, a zero descriptor and a false flag under ``_KLT_HAS_DESC``.  Under
+    ``cfg.klt_corner_describe`` they are also described (:func:`visualodometry_amd.brief.describe`,
+    from the keyframe's pyramid tag) and the keyframe keeps (N, 8) uint32 rows under ``_KLT_BRIEF``,
+    zeros for the rows that have a descriptor."""
     from .. import corners
 
     kf = vo.keyframe
@@ -647,39 +702,65 @@ def klt_replenish_corners(vo, st: KltTracker, feats: dict) -> int:
     full["keypoints"] = cat(kp, add)
     full["descriptors"] = cat(des, np.zeros((len(add), des_rows.shape[1]), np.float32))
     full[_KLT_HAS_DESC] = np.concatenate([had, np.zeros(len(add), bool)])
+    if st.describe:
+        from .. import brief
+
+        old = np.asarray(feats[_KLT_BRIEF], np.uint32) if _KLT_BRIEF in feats else \
+            np.zeros((n_kept, brief.WORDS), np.uint32)
+        new = brief.describe(feats[_KLT_IMAGE], add, tag=feats[_KLT_TAG])[0] if len(add) else old[:0]
+        full[_KLT_BRIEF] = np.concatenate([old, new])
     ids = np.asarray(kf["ids"])
     kf["feats"] = full
     kf["ids"] = np.concatenate([ids, np.full(len(add), -1, ids.dtype)])
     return int(len(add))
 
 
-def klt_descriptor_rows(feats0: dict, feats1: dict, match):
+def klt_descriptor_rows(feats0: dict, feats1: dict, match, brief=None):
     """``match_frames`` between dicts of which one has rows without a descriptor
     (``cfg.klt_corner_replenish``): ``match(sub0, sub1)`` over dicts of the rows that have one, the
-    indices mapped back; an empty (0, 2) array when a side has none.  ``None`` when neither dict is
-    flagged."""
+    indices mapped back; no pairs from that part when a side has none.  ``None`` when neither dict
+    is flagged.
+
+    ``brief`` (``cfg.klt_corner_describe``: the :class:`KltTracker`) adds the pairs of the rows
+    without a descriptor when both dicts carry BRIEF rows: ``matcher.match_hamming`` between the two
+    sets of corner rows, ratio ``klt_brief_ratio``, ``klt_brief_max_dist`` and the cross check, mapped
+    back likewise.  Descriptor rows and corner rows are disjoint on both sides, so the union is as
+    one-to-one as its parts; it comes out in ascending keyframe row order."""
     flagged = [isinstance(f, dict) and _KLT_HAS_DESC in f for f in (feats0, feats1)]
     if not any(flagged):
         return None
-    rows, subs = [], []
+    rows, subs, empty = [], [], False
     for f, has in zip((feats0, feats1), flagged):
         if not has:
             rows.append(None)
             subs.append(f)
             continue
         idx = np.flatnonzero(np.asarray(f[_KLT_HAS_DESC], bool))
-        if idx.size == 0:
-            return np.zeros((0, 2), np.int64)
+        empty = empty or idx.size == 0
         kp = f["keypoints"]
         sub = {k: v for k, v in f.items() if not k.startswith("_vo_amd_klt")}
         sub["keypoints"] = _batched(_rows(kp[0] if getattr(kp, "ndim", 2) == 3 else kp, idx), kp)
         sub["descriptors"] = _batched(_rows(_descriptors(f), idx), f["descriptors"])
         rows.append(idx)
         subs.append(sub)
-    pairs = np.asarray(_np(match(subs[0], subs[1])), np.int64).reshape(-1, 2)
-    for side in (0, 1):
-        if rows[side] is not None:
-            pairs[:, side] = rows[side][pairs[:, side]]
+    if empty:
+        pairs = np.zeros((0, 2), np.int64)
+    else:
+        pairs = np.asarray(_np(match(subs[0], subs[1])), np.int64).reshape(-1, 2)
+        for side in (0, 1):
+            if rows[side] is not None:
+                pairs[:, side] = rows[side][pairs[:, side]]
+    if brief is not None and all(flagged) and _KLT_BRIEF in feats0 and _KLT_BRIEF in feats1:
+        from .. import matcher
+
+        crows = [np.flatnonzero(~np.asarray(f[_KLT_HAS_DESC], bool)) for f in (feats0, feats1)]
+        if crows[0].size and crows[1].size:
+            more = matcher.match_hamming(np.asarray(feats0[_KLT_BRIEF], np.uint32)[crows[0]],
+                                         np.asarray(feats1[_KLT_BRIEF], np.uint32)[crows[1]], ratio=brief.brief_ratio,
+                                         max_dist=brief.brief_max_dist, cross_check=True)
+            more = np.asarray(more, np.int64).reshape(-1, 2)
+            both = np.concatenate([pairs, np.stack([crows[0][more[:, 0]], crows[1][more[:, 1]]], 1)])
+            pairs = both[np.argsort(both[:, 0], kind="stable")]
     return pairs
 
 
@@ -854,7 +935,9 @@ def _wrap_match_frames(orig):
             pairs = klt_pairs(feats0, feats1)
             if pairs is not None:
                 return pairs
-            pairs = klt_descriptor_rows(feats0, feats1, lambda a, b: plain(self, a, b))  # cfg.klt_corner_replenish
+            st = self.__dict__["_vo_amd_klt"]
+            pairs = klt_descriptor_rows(feats0, feats1, lambda a, b: plain(self, a, b),  # cfg.klt_corner_replenish
+                                        st if st.describe else None)  # cfg.klt_corner_describe
             if pairs is not None:
                 return pairs
         return plain(self, feats0, feats1)

@@ -378,6 +378,113 @@ def match_knn2(des0, des1, ctx: _lib.Context | None = None):
     return idx, dist
 
 
+HAMMING_RATIO = 0.8
+HAMMING_MAX_WORDS = 16
+
+
+def _as_bits(d) -> np.ndarray:
+    """Binary rows as contiguous uint32 (n, words): uint32 / int32 as they are, uint8 (n, 4 words)
+    viewed (OpenCV's layout of ORB / BRIEF rows, little endian)."""
+    if hasattr(d, "detach"):
+        d = d.detach().cpu().numpy()
+    d = np.asarray(d)
+    if d.ndim != 2:
+        raise ValueError(f"binary descriptors must be (N, words), got shape {d.shape}")
+    if d.dtype == np.uint8:
+        if d.shape[1] % 4:
+            raise ValueError(f"uint8 binary descriptors must have a multiple of 4 columns, got {d.shape[1]}")
+        return np.ascontiguousarray(d).view(np.uint32)
+    if d.dtype not in (np.uint32, np.int32):
+        raise ValueError(f"binary descriptors must be uint32, int32 or uint8, got {d.dtype}")
+    return np.ascontiguousarray(d).view(np.uint32)
+
+
+def _device_bits(d, ctx):
+    """(pointer, n, words, keep-alive) of rows already on the context's GPU, or None: a
+    :class:`_lib.DeviceArray` of 32-bit words, or a torch int32 tensor on ``cuda:<ctx.device>``."""
+    if isinstance(d, _lib.DeviceArray):
+        if len(d.shape) != 2 or d.dtype.itemsize != 4:
+            raise ValueError("a DeviceArray of binary descriptors must be (N, words) of 32-bit words")
+        return d.ptr, d.shape[0], d.shape[1], d
+    if getattr(d, "is_cuda", False) and d.device.index == ctx.device and not getattr(ctx, "_foreign_tensors", False):
+        import torch
+
+        if d.dtype != torch.int32 or d.dim() != 2:
+            raise ValueError("a CUDA tensor of binary descriptors must be int32 (N, words)")
+        t = d.detach().contiguous()
+        return t.data_ptr(), t.shape[0], t.shape[1], t
+    return None
+
+
+def match_hamming(des0, des1, ratio: float = HAMMING_RATIO, max_dist=None, cross_check: bool = False,
+                  return_dist: bool = False, return_knn: bool = False, ctx: _lib.Context | None = None):
+    """Brute-force Hamming matching of binary descriptors (``vo_match_hamming``): the structure of
+    ``cv2.BFMatcher(cv2.NORM_HAMMING)`` with ``knnMatch(k=2)`` and a ratio test; see
+    ``include/vo_hip.h`` for the exact keys and the keep rule.
+
+    ``des0``, ``des1``: numpy ``uint32 (n, words)`` (:func:`visualodometry_amd.brief.describe`'s
+    rows) or ``uint8 (n, 4 words)``, ``words`` in 1..16.  Both being torch int32 tensors on the
+    context's GPU (or :class:`_lib.DeviceArray`), they are read in place; the call falls back to
+    host arrays as :func:`match_knn2_ratio` does when the library refuses torch's pointers.
+    ``max_dist`` ``None`` or 0 is not tested.  ``cross_check``: a kept pair ``(i, j)`` survives only
+    if ``i`` is the nearest query row of ``j`` (ties to the lower ``i``); the pairs are then
+    one-to-one.
+
+    Returns ``(M, 2)`` int64 (query, train) pairs in ascending query order; with ``return_dist`` also
+    their int32 distances; with ``return_knn`` also ``(idx (n0, 2) int32, dist (n0, 2) int32)``, -1
+    and ``INT32_MAX`` where no neighbour exists."""
+    on_device = [isinstance(d, _lib.DeviceArray) or bool(getattr(d, "is_cuda", False)) for d in (des0, des1)]
+    if all(on_device):
+        ctx = ctx or _lib.context()
+    d0, d1 = (_device_bits(des0, ctx), _device_bits(des1, ctx)) if all(on_device) else (None, None)
+    dev = d0 is not None and d1 is not None
+    if dev:
+        (p0, n0, words, _k0), (p1, n1, w1, _k1) = d0, d1
+        if any(hasattr(d, "is_cuda") for d in (des0, des1)):
+            import torch
+
+            torch.cuda.current_stream(torch.device("cuda", ctx.device)).synchronize()  # the tensors' producer is done
+    else:
+        a = des0.numpy() if isinstance(des0, _lib.DeviceArray) else _as_bits(des0)
+        b = des1.numpy() if isinstance(des1, _lib.DeviceArray) else _as_bits(des1)
+        a, b = np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32)
+        (n0, words), (n1, w1) = a.shape, b.shape
+        p0, p1 = a.ctypes.data, b.ctypes.data
+    if words != w1:
+        raise ValueError(f"descriptor widths differ: {words} vs {w1} words")
+    if not 1 <= words <= HAMMING_MAX_WORDS:
+        raise ValueError(f"binary descriptors must have 1..{HAMMING_MAX_WORDS} 32-bit words, got {words}")
+    kidx = np.full((n0, 2), -1, np.int32)
+    kdist = np.full((n0, 2), np.iinfo(np.int32).max, np.int32)
+    if n0 == 0 or n1 == 0:  # nothing to match: no device is needed
+        res = [np.empty((0, 2), np.int64)] + ([np.empty(0, np.int32)] if return_dist else []) + \
+            ([(kidx, kdist)] if return_knn else [])
+        return res[0] if len(res) == 1 else tuple(res)
+    ctx = ctx or _lib.context()
+    flags = (_lib.VO_MATCH_HAMMING_MUTUAL if cross_check else 0) | (_lib.VO_MATCH_DEVICE_PTRS if dev else 0)
+    opt = _lib.MatchHammingOptionsC(ratio=float(ratio), max_dist=int(max_dist or 0), flags=flags, reserved=0)
+    out = np.empty((n0, 2), dtype=np.int32)
+    dist = np.empty(n0, dtype=np.int32)
+    cnt = np.zeros(1, dtype=np.int32)
+    rc = ctx.lib.vo_match_hamming(ctx.handle, C.c_void_p(p0), n0, C.c_void_p(p1), n1,
+                                  words, C.byref(opt), out.ctypes.data, dist.ctypes.data, ptr(cnt, C.c_int32),
+                                  kidx.ctypes.data if return_knn else None, kdist.ctypes.data if return_knn else None)
+    if dev and rc == _lib.VO_ERR_ARG and hasattr(des0, "is_cuda") and hasattr(des1, "is_cuda"):
+        # torch's device memory is not this library's HIP runtime's (the library refuses such
+        # pointers before any launch): the host path from here on
+        ctx._foreign_tensors = True
+        return match_hamming(des0.detach().cpu(), des1.detach().cpu(), ratio, max_dist, cross_check, return_dist,
+                             return_knn, ctx)
+    check(rc, "vo_match_hamming")
+    m = int(cnt[0])
+    res = [out[:m].astype(np.int64)]
+    if return_dist:
+        res.append(dist[:m].copy())
+    if return_knn:
+        res.append((kidx, kdist))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def match_batch_device(des0: _lib.DeviceArray, des1: _lib.DeviceArray, ratio: float = RATIO_THRESH,
                        out: _lib.DeviceArray | None = None, ctx: _lib.Context | None = None,
                        cross_check: bool = False):
